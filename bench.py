@@ -77,7 +77,17 @@ def parse():
                          "headline's hold-out AuPR must equal the fp32 model's), or lossy bf16 on the bf16 matrix "
                          "cores (BASELINE config 2, lr-rf-1m '1 MI355X bf16'); tree learners bin their inputs "
                          "either way")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed train returned (the selector's CV, train "
+                         "and hold-out metrics and the selected model's fitted state) as DIR/<name>.npy, float32 or "
+                         "float64, at most 64 MB in all; the inputs are seeded, so two builds can be compared "
+                         "output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what goes beyond the headline figure (the --verbose per-stage and per-phase "
+                         "timings); a plain run sets up, warms up, times the steps and prints the result line")
     a = ap.parse_args()
+    if a.full:
+        a.verbose = True
     if a.config == "lr-rf-1m" and a.models == "default":
         a.models = "OpLogisticRegression,OpRandomForestClassifier"
     if a.dtype is None:         # BASELINE.json names bf16 for config 2 only
@@ -124,6 +134,97 @@ def build_workflow(args, ds, label, preds, reader=None):
     return wf, pred
 
 
+DUMP_BYTES = 64_000_000      # --dump-outputs writes at most this much in all
+
+
+def _numbers(obj, out):
+    """The numeric leaves of a JSON-like value, dict keys in sorted order (strings, None and flags skipped)."""
+    if isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            _numbers(obj[k], out)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _numbers(v, out)
+    elif isinstance(obj, (int, float)) and not isinstance(obj, bool):
+        out.append(float(obj))
+    return out
+
+
+def _state_arrays(obj, prefix, out):
+    """Every tensor / array of a fitted learner state as ``name -> numpy array``; plain numbers of one dict
+    are collected under ``<prefix>_scalars``."""
+    import numpy as np
+    import torch
+    if isinstance(obj, torch.Tensor):
+        t = obj.detach()
+        t = t.to(torch.float32) if t.dtype in (torch.float16, torch.bfloat16) else t
+        out[prefix] = t.cpu().numpy()
+    elif isinstance(obj, np.ndarray):
+        if obj.dtype.kind in "fiub":
+            out[prefix] = obj
+    elif isinstance(obj, dict):
+        scalars = []
+        for k in sorted(obj, key=str):
+            v = obj[k]
+            if isinstance(v, (int, float)) and not isinstance(v, bool):
+                scalars.append(float(v))
+            else:
+                _state_arrays(v, f"{prefix}_{k}", out)
+        if scalars:
+            out[prefix + "_scalars"] = np.asarray(scalars, np.float64)
+    elif isinstance(obj, (list, tuple)):
+        if obj and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in obj):
+            out[prefix] = np.asarray(obj, np.float64)
+        else:
+            for i, v in enumerate(obj):
+                _state_arrays(v, f"{prefix}_{i}", out)
+    return out
+
+
+def collect_outputs(model, pred):
+    """What a caller of the timed ``OpWorkflow.train()`` receives, as named host arrays: the selector summary's
+    metrics (one row per evaluated grid point, then the winner's train and hold-out evaluation) and the selected
+    model's fitted state."""
+    import numpy as np
+    sel = model.get_origin_stage_of(pred)
+    summ = sel.metadata.get("summary", {})
+    rows = [_numbers(r.get("metricValues"), []) for r in summ.get("validationResults") or []]
+    width = max((len(r) for r in rows), default=0)
+    out = {"cv_metrics": np.asarray([r + [float("nan")] * (width - len(r)) for r in rows], np.float64),
+           "train_evaluation": np.asarray(_numbers(summ.get("trainEvaluation"), []), np.float64),
+           "holdout_evaluation": np.asarray(_numbers(summ.get("holdoutEvaluation"), []), np.float64)}
+    _state_arrays(getattr(sel, "state", None), "model", out)
+    return out
+
+
+def write_outputs(arrays, directory):
+    """``DIR/<name>.npy`` in float32 or float64; an array over its share of the 64 MB keeps a fixed, seeded sample
+    of its elements (sorted positions of the flattened array)."""
+    import re
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name in sorted(arrays):
+        a = np.asarray(arrays[name])
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        keep = share // a.dtype.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, re.sub(r"[^A-Za-z0-9_.-]", "_", name) + ".npy"), np.ascontiguousarray(a))
+
+
+def _read_only_tree():
+    """A tree built by another user: the libraries directory cannot be written, so no build lock can be taken.
+    The built libraries are then loaded as they are (``ops/_native.py`` still checks that each carries the hash of
+    the sources next to it; a stale or missing one cannot be rebuilt there and is an error) -- also by a build of
+    the package whose ``build_host`` / ``build_hip`` take the lock before they look at the library."""
+    import contextlib
+    from transmogrifai_amd.ops import build as B
+    if not os.access(B.LIB, os.W_OK):
+        B._Lock = contextlib.nullcontext
+
+
 def _spawned_rank(local_rank, n, port, argv):
     """Entry of a rank process started by ``bench.py --gpus N`` without torchrun."""
     os.environ.update(RANK=str(local_rank), LOCAL_RANK=str(local_rank), WORLD_SIZE=str(n),
@@ -153,6 +254,7 @@ def main():
     from transmogrifai_amd import config as CFG
     from transmogrifai_amd.parallel import dist as D
 
+    _read_only_tree()
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     use_gpu = args.device != "cpu" and torch.cuda.is_available()
@@ -167,7 +269,8 @@ def main():
         # exchange is answered by tiling this rank's records (tree_grow_hip.hip tmog_hip_fp_allgather)
         D.simulate(int(os.environ.get("TMOG_SIM_RANK", "0")), int(sim))
     else:
-        D.init_from_env(device_id=local_rank if use_gpu else None)
+        # a --device cpu run talks gloo also where a GPU is present (several CPU ranks cannot share one GPU's RCCL)
+        D.init_from_env(backend=None if use_gpu else "gloo", device_id=local_rank if use_gpu else None)
     world = D.world()
     if world != max(1, args.gpus) and args.device != "cpu" and not sim:
         raise SystemExit(f"bench.py --gpus {args.gpus} but the process group has {world} ranks")
@@ -209,8 +312,9 @@ def main():
     gc_steps = []
 
     pq_path = [None]
+    dumped = [None]             # --dump-outputs: the last timed train's outputs as host arrays
 
-    def one_run():
+    def one_run(collect=False):
         uid.reset(0)
         ds, label, preds = make_table()
         n_raw[0] = len(preds)
@@ -265,13 +369,15 @@ def main():
         if os.environ.get("TMOG_MEM_TRACE") == "1" and D.rank() == 0:
             st = model.train_timings.get("stages", {})
             print(json.dumps({k: v for k, v in st.items() if k.startswith("peak_gb")}), flush=True)
+        if collect and (D.rank() == 0 or sim):
+            dumped[0] = collect_outputs(model, pred)
         return dt, ho, summ
 
     expected_configs = _expected_configs(args)
     if args.ingest != "memory" and world > 1:
         raise SystemExit("--ingest parquet / csv is a single-GPU measurement")
     try:
-        _timed(args, one_run, expected_configs, use_gpu, dev, torch, D, sim, n_raw, stage_t, gc_steps, world)
+        _timed(args, one_run, expected_configs, use_gpu, dev, torch, D, sim, n_raw, stage_t, gc_steps, world, dumped)
     finally:
         if pq_path[0] and os.path.exists(pq_path[0]):
             os.remove(pq_path[0])
@@ -280,16 +386,18 @@ def main():
         dist.destroy_process_group()
 
 
-def _timed(args, one_run, expected_configs, use_gpu, dev, torch, D, sim, n_raw, stage_t, gc_steps, world):
+def _timed(args, one_run, expected_configs, use_gpu, dev, torch, D, sim, n_raw, stage_t, gc_steps, world, dumped):
     for _ in range(args.warmup):
         one_run()
     if use_gpu:
         torch.cuda.reset_peak_memory_stats(dev)
     times, auprs, summ = [], [], None
-    for _ in range(args.steps):
-        dt, ho, summ = one_run()
+    for i in range(args.steps):
+        dt, ho, summ = one_run(collect=bool(args.dump_outputs) and i == args.steps - 1)
         times.append(dt)
         auprs.append(ho)
+    if dumped[0] is not None:
+        write_outputs(dumped[0], args.dump_outputs)
     t = torch.tensor([sum(times)], dtype=torch.float64)
     t = D.all_reduce(t, "max")
     total = float(t.item())

@@ -14,7 +14,8 @@ from transmogrifai_amd.selector.factories import RegressionModelSelector  # noqa
 from transmogrifai_amd.tuning.splitters import DataSplitter  # noqa: E402
 from transmogrifai_amd.workflow.workflow import OpWorkflow  # noqa: E402
 
-DEFAULT = "/root/reference/helloworld/src/main/resources/BostonDataset/housing.data"
+DEFAULT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference",
+                       "helloworld", "src", "main", "resources", "BostonDataset", "housing.data")
 COLS = ["crim", "zn", "indus", "chas", "nox", "rm", "age", "dis", "rad", "tax", "ptratio", "b", "lstat", "medv"]
 
 

@@ -22,7 +22,8 @@ from transmogrifai_amd.workflow.workflow import OpWorkflow  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from dataprep_joins_aggregates import DAY, parse_ts  # noqa: E402
 
-DATA = "/root/reference/helloworld/src/main/resources/WebVisitsDataset/WebVisits.csv"
+DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference",
+                    "helloworld", "src", "main", "resources", "WebVisitsDataset", "WebVisits.csv")
 VISIT = [("userId", "string"), ("url", "string"), ("productId", "int"), ("price", "double"),
          ("timestamp", "string")]
 

@@ -28,7 +28,8 @@ from transmogrifai_amd.readers.files import DataReaders  # noqa: E402
 from transmogrifai_amd.readers.joined import JoinedReader, JoinTypes  # noqa: E402
 from transmogrifai_amd.workflow.workflow import OpWorkflow  # noqa: E402
 
-DATA = "/root/reference/helloworld/src/main/resources/EmailDataset"
+DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference",
+                    "helloworld", "src", "main", "resources", "EmailDataset")
 DAY = 86_400_000
 CLICK = [("clickId", "int"), ("userId", "int"), ("emailId", "int"), ("timeStamp", "string")]
 SEND = [("sendId", "int"), ("userId", "int"), ("emailId", "int"), ("timeStamp", "string")]

@@ -14,7 +14,8 @@ from transmogrifai_amd.selector.factories import MultiClassificationModelSelecto
 from transmogrifai_amd.tuning.splitters import DataCutter  # noqa: E402
 from transmogrifai_amd.workflow.workflow import OpWorkflow  # noqa: E402
 
-DEFAULT = "/root/reference/helloworld/src/main/resources/IrisDataset/iris.data"
+DEFAULT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference",
+                       "helloworld", "src", "main", "resources", "IrisDataset", "iris.data")
 SCHEMA = [("sepalLength", "double"), ("sepalWidth", "double"), ("petalLength", "double"),
           ("petalWidth", "double"), ("irisClass", "string")]
 

@@ -25,7 +25,8 @@ SCHEMA = [("id", "int"), ("survived", "int"), ("pClass", "int"), ("name", "strin
           ("age", "double"), ("sibSp", "int"), ("parCh", "int"), ("ticket", "string"), ("fare", "double"),
           ("cabin", "string"), ("embarked", "string")]
 
-DEFAULT_CSV = "/root/reference/test-data/PassengerDataAll.csv"
+DEFAULT_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference",
+                           "test-data", "PassengerDataAll.csv")
 
 
 def build(lr_only: bool = True, seed=None):

@@ -39,8 +39,11 @@ def _score(vec, ds):
     return out[vec.name].values.double().tolist(), None
 
 
-@pytest.mark.parametrize("moment", [_ms(2017, 9, 28, 15, 45, 39),
-                                    int((dt.datetime.now(UTC) - dt.timedelta(hours=1)).timestamp() * 1000)])
+# the moment taken from the clock gets a fixed id: a test id must not change from one collection to the next
+HOUR_AGO = pytest.param(int((dt.datetime.now(UTC) - dt.timedelta(hours=1)).timestamp() * 1000), id="an-hour-ago")
+
+
+@pytest.mark.parametrize("moment", [_ms(2017, 9, 28, 15, 45, 39), HOUR_AGO])
 def test_vectorize_dates_at(moment):
     ds, (f1, f2, f3) = TestFeatureBuilder.of(
         ("f1", T.DateTime, [1, 1, None]),
@@ -80,8 +83,7 @@ def _map_expected(m):
             [0, _tdiv(m, DAY), -100]]
 
 
-@pytest.mark.parametrize("moment", [_ms(2017, 9, 28, 15, 45, 39), _ms(1901, 1, 1, 0, 0, 0),
-                                    int((dt.datetime.now(UTC) - dt.timedelta(hours=1)).timestamp() * 1000)])
+@pytest.mark.parametrize("moment", [_ms(2017, 9, 28, 15, 45, 39), _ms(1901, 1, 1, 0, 0, 0), HOUR_AGO])
 def test_date_map_vectorize_at(moment):
     ds, (f1,) = _map_ds(moment)
     v1 = f1.vectorize(default_value=0, reference_date=moment, track_nulls=False, circular_date_reps=())

@@ -21,7 +21,7 @@ from transmogrifai_amd.features.builder import FeatureBuilder
 from transmogrifai_amd.insights import model_insights as MI
 from transmogrifai_amd.insights.model_insights import ModelInsights
 
-AVRO = "/root/reference/test-data/PassengerData.avro"
+AVRO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "test-data", "PassengerData.avro")
 pytestmark = pytest.mark.skipif(not os.path.exists(AVRO), reason="reference test data not mounted")
 
 

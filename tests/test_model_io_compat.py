@@ -23,8 +23,8 @@ from transmogrifai_amd.features.builder import FeatureBuilder
 from transmogrifai_amd.readers.avro import read_avro
 from transmogrifai_amd.workflow.workflow import OpWorkflow, OpWorkflowModel
 
-REF = "/root/reference/core/src/test/resources"
-PASSENGERS = "/root/reference/test-data/PassengerData.avro"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "core", "src", "test", "resources")
+PASSENGERS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "test-data", "PassengerData.avro")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DAY_MS = 86400000
 

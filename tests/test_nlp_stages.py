@@ -83,7 +83,7 @@ def test_mime_detector_reference_fixtures():
     import os
     import pytest
     from transmogrifai_amd.stages.feature.nlp_stages import MimeTypeDetector
-    ref = "/root/reference"
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
     names = ["core/src/test/resources/811harmo24to36.mp3", "core/src/test/resources/820orig36to48.wav",
              "core/src/test/resources/face.png", "features/src/test/resources/log4j.properties",
              "core/src/test/resources/note.xml", "core/src/test/resources/RunnerParams.json",

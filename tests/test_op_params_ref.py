@@ -6,7 +6,7 @@ import pytest
 
 from transmogrifai_amd.workflow.params import OpParams, ReaderParams
 
-RES = "/root/reference/features/src/test/resources"
+RES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "features", "src", "test", "resources")
 pytestmark = pytest.mark.skipif(not os.path.isdir(RES), reason="reference resources not present")
 
 

@@ -10,7 +10,7 @@ from transmogrifai_amd.features.aggregators import CutOffTime
 from transmogrifai_amd.readers.files import CSVReader, DataReaders
 from transmogrifai_amd.readers.aggregate import AggregateParams, ConditionalParams, TimeStampToKeep
 
-REF = "/root/reference/test-data"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "test-data")
 have_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference test data not mounted")
 
 
@@ -110,7 +110,7 @@ def test_avro_roundtrip(tmp_path):
 def _join_fixture():
     import csv
     from transmogrifai_amd.readers.base import InMemoryReader
-    ref = "/root/reference/test-data"
+    ref = REF
     left = [dict(id=r[0], timestamp=int(r[1]), description=r[2]) for r in csv.reader(open(f"{ref}/SparkExampleJoin.csv"))]
     right = [dict(sparkId=r[0], timestamp=int(r[1]), description=r[2], id=int(r[3]))
              for r in csv.reader(open(f"{ref}/JoinTestData.csv"))]

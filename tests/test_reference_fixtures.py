@@ -20,7 +20,7 @@ from transmogrifai_amd.features import types as T
 from transmogrifai_amd.testkit.feature_builder import TestFeatureBuilder
 from transmogrifai_amd.testkit.spec import check_estimator, check_transformer
 
-REF = "/root/reference"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
 FIXTURE = f"{REF}/core/src/test/resources/OldModelVersion_0_7_1/op-model.json/part-00000"
 
 

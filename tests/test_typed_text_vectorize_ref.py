@@ -13,7 +13,7 @@ from transmogrifai_amd.testkit.feature_builder import TestFeatureBuilder
 from transmogrifai_amd.testkit.random_data import RandomText
 from transmogrifai_amd.workflow.workflow import OpWorkflow
 
-REF = "/root/reference"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
 FILES = ["core/src/test/resources/811harmo24to36.mp3", "core/src/test/resources/820orig36to48.wav",
          "core/src/test/resources/face.png", "features/src/test/resources/log4j.properties",
          "core/src/test/resources/note.xml", "core/src/test/resources/RunnerParams.json",

@@ -8,12 +8,15 @@ training rows (no workflow CV) every fold's validation rows were seen by the buc
 metric is inflated; with workflow CV the bucketizers of each fold never see the fold's validation
 labels and every grid point's CV AuPR is lower.
 """
+import os
+
 import pandas as pd
 import pytest
 
 from transmogrifai_amd.features.builder import FeatureBuilder
 
-CSV = "/root/reference/test-data/PassengerDataAllWithHeader.csv"
+CSV = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "test-data",
+                   "PassengerDataAllWithHeader.csv")
 
 
 def _records():

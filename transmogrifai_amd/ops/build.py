@@ -116,6 +116,8 @@ class _Lock:
 
 def build_host(force: bool = False) -> Path:
     srcs = _sources("host")
+    if not force and not _stale(HOST_SO, "host"):
+        return HOST_SO          # up to date: nothing to write, so a tree this user cannot write to still loads
     with _Lock():
         if force or _stale(HOST_SO, "host"):
             tmp = HOST_SO.with_suffix(f".so.tmp{os.getpid()}")
@@ -135,6 +137,8 @@ def build_hip(force: bool = False, arch: str = ARCH) -> Path:
     hipcc = hipcc_path()
     if hipcc is None:
         raise RuntimeError("hipcc not found: cannot build the HIP kernels")
+    if not force and not _stale(HIP_SO, "hip"):
+        return HIP_SO           # up to date: no lock file needed (the tree may be read-only for this user)
     with _Lock():
         if force or _stale(HIP_SO, "hip"):
             from concurrent.futures import ThreadPoolExecutor

@@ -13,7 +13,10 @@ from typing import List, Optional
 
 from ..features.builder import FeatureBuilder
 
-TEST_DATA = os.environ.get("TMOG_REFERENCE_TEST_DATA", "/root/reference/test-data")
+# the fixture's data files are kept with the test suite (tests/golden/reference mirrors the reference's layout)
+TEST_DATA = os.environ.get("TMOG_REFERENCE_TEST_DATA", os.path.join(
+    os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+    "tests", "golden", "reference", "test-data"))
 CUTOFF_S = 1471046600
 PASSENGER_TYPE = "com.salesforce.op.test.Passenger"     # the record type name reader params are keyed by
 
