@@ -3,13 +3,18 @@
 // the device, where
 //   csv_fields_kernel   one wave per row walks the row in 64-byte windows (coalesced loads), finds the separators
 //                       outside double quotes with two ballots (the quote parity of each lane is the popcount of
-//                       the quotes below it) and writes every field's start offset;
+//                       the quotes below it) and writes every field's start offset; a row that ends inside quotes
+//                       (a newline in a quoted field) is reported with nfields = -1;
 //   csv_parse_num       one thread per (row, column): the field as a float64 or int64 with a validity byte --
 //                       pandas' NA strings and empty cells are missing; decimal strings of at most 19 significant
 //                       digits with |exponent| <= 22 convert exactly (one IEEE multiply or divide of two exact
 //                       doubles: the correctly rounded result), anything else is flagged for the host parser;
-//   csv_hash_text       one thread per (row, column): a 64-bit hash of the unquoted field bytes (0 = missing), the
-//                       input of the device dictionary encoding (torch.unique + first appearance).
+//   csv_hash_text       one thread per (row, column): a 64-bit hash of the decoded field bytes (0 = missing), the
+//                       input of the device dictionary encoding (stable sort + first appearance), and a second,
+//                       independent hash that tells two strings with one first hash apart.
+// A cell's value follows pyarrow's CSV reader: a field whose first and last raw bytes are double quotes is quoted
+// (the quotes go, "" inside is one quote); any other field is literal, padding and quotes included. Numbers are
+// parsed from the value with spaces and tabs trimmed; the NA strings are compared with the untrimmed value.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -19,7 +24,8 @@ __device__ __forceinline__ uint64_t lanes_below(int lane) { return lane ? (~0ull
 
 // buf: the chunk's bytes; row_start[r] .. row_end[r] (exclusive, the '\n' or the chunk end) are row r's bytes (a
 // trailing '\r' is dropped). fstart[r * (ncols + 1) + k] = absolute offset of field k, fstart[.. + nf] = end + 1 (so
-// field k is [fstart[k], fstart[k + 1] - 1)); nfields[r] = number of fields (fields past ncols are not recorded).
+// field k is [fstart[k], fstart[k + 1] - 1)); nfields[r] = number of fields (fields past ncols are not recorded), or
+// -1 when the row ends inside quotes: its newline belongs to a quoted field, which this reader does not parse.
 __global__ void __launch_bounds__(256) csv_fields_kernel(const uint8_t* __restrict__ buf,
                                                          const int64_t* __restrict__ row_start,
                                                          const int64_t* __restrict__ row_end, int64_t nrows,
@@ -51,13 +57,14 @@ __global__ void __launch_bounds__(256) csv_fields_kernel(const uint8_t* __restri
   }
   if (lane == 0) {
     fs[min(nf, ncols)] = e + 1;
-    nfields[r] = nf;
+    nfields[r] = quote ? -1 : nf;
   }
 }
 
 __device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || c == '\t'; }
 
-// pandas.read_csv's default NA strings (readers/columnar.py _PANDAS_NA), compared on the trimmed, unquoted field
+// pandas.read_csv's default NA strings (readers/columnar.py _PANDAS_NA), compared with the cell's value
+// (unquoted, not trimmed)
 __device__ bool is_na(const uint8_t* s, int n) {
   if (n == 0) return true;
   if (n > 8) return false;
@@ -77,19 +84,20 @@ __device__ bool is_na(const uint8_t* s, int n) {
   return false;
 }
 
-// the field's trimmed, unquoted byte range
-__device__ __forceinline__ void field_range(const uint8_t* buf, const int64_t* fs, int nf, int col, int64_t* a,
-                                            int64_t* b) {
+// the value of field col of a row: its raw bytes, without the quotes when the first and the last byte are quotes
+// (*quoted: "" inside is an escape); an absent field (col >= nf, or a row reported as -1) is empty
+__device__ __forceinline__ void field_value(const uint8_t* buf, const int64_t* fs, int nf, int col, int64_t* a,
+                                            int64_t* b, bool* quoted) {
+  *quoted = false;
   if (col >= nf) {
     *a = *b = 0;
     return;
   }
   int64_t s = fs[col], t = fs[col + 1] - 1;
-  while (s < t && is_space(buf[s])) ++s;
-  while (t > s && is_space(buf[t - 1])) --t;
   if (t - s >= 2 && buf[s] == '"' && buf[t - 1] == '"') {
     ++s;
     --t;
+    *quoted = true;
   }
   *a = s;
   *b = t;
@@ -115,21 +123,30 @@ __global__ void __launch_bounds__(256) csv_parse_num_kernel(const uint8_t* __res
   const int j = (int)(i - r * nout);
   const int64_t o = i;
   int64_t a, b;
-  field_range(buf, fstart + r * (int64_t)(ncols + 1), nfields[r], cols[j], &a, &b);
+  bool quoted;
+  field_value(buf, fstart + r * (int64_t)(ncols + 1), nfields[r], cols[j], &a, &b, &quoted);
+  const int64_t ua = a, ub = b;         // the untrimmed value: what the NA strings are compared with
+  slow[o] = 0;
+  valid[o] = 0;
+  out[o] = 0;
+  if (a == b) return;                   // an empty cell (or ""): missing
+  while (a < b && is_space(buf[a])) ++a;
+  while (b > a && is_space(buf[b - 1])) --b;
   const uint8_t* s = buf + a;
   const int n = (int)(b - a);
-  slow[o] = 0;
-  if (n == 0) {
-    valid[o] = 0;
-    out[o] = 0;
+  if (n == 0) {                         // only padding: not a number and not NA, the host rejects it
+    slow[o] = 1;
     return;
   }
   int k = 0;
-  bool neg = false;
-  if (s[k] == '+' || s[k] == '-') neg = s[k++] == '-';
+  bool neg = false, plus = false;
+  if (s[k] == '+' || s[k] == '-') {
+    neg = s[k] == '-';
+    plus = s[k++] == '+';
+  }
   uint64_t m = 0;
   int nd = 0, e10 = 0;
-  bool any = false, dot = false, bad = false;
+  bool any = false, dot = false, bad = false, hasexp = false;
   for (; k < n; ++k) {
     const uint8_t c = s[k];
     if (c >= '0' && c <= '9') {
@@ -154,6 +171,7 @@ __global__ void __launch_bounds__(256) csv_parse_num_kernel(const uint8_t* __res
   }
   if (k < n && (s[k] == 'e' || s[k] == 'E') && any) {
     ++k;
+    hasexp = true;
     bool eneg = false;
     if (k < n && (s[k] == '+' || s[k] == '-')) eneg = s[k++] == '-';
     int ev = 0;
@@ -166,23 +184,15 @@ __global__ void __launch_bounds__(256) csv_parse_num_kernel(const uint8_t* __res
     e10 += eneg ? -ev : ev;
   }
   if (!any || k != n) {                 // not a plain decimal: an NA string is missing, anything else (inf,
-    if (is_na(s, n)) {                  // hex, stray characters) goes to the host parser
-      valid[o] = 0;
-      out[o] = 0;
-      return;
-    }
+    if (is_na(buf + ua, (int)min(ub - ua, (int64_t)9))) return;       // hex, stray characters) goes to the host
     bad = true;
   }
-  if (kind[j] == 1) {                   // int64: an integer literal (a ".0" fraction is accepted)
-    if (bad || e10 < 0 || nd + e10 > 18) {
+  if (kind[j] == 1) {                   // int64: plain [-]digits; '+', a fraction (".0" too) or an exponent: host
+    if (bad || plus || dot || hasexp || nd > 18) {
       slow[o] = 1;
-      valid[o] = 0;
-      out[o] = 0;
       return;
     }
-    int64_t v = (int64_t)m;
-    for (int t = 0; t < e10; ++t) v *= 10;
-    out[o] = neg ? -v : v;
+    out[o] = neg ? -(int64_t)m : (int64_t)m;
     valid[o] = 1;
     return;
   }
@@ -194,8 +204,6 @@ __global__ void __launch_bounds__(256) csv_parse_num_kernel(const uint8_t* __res
     v = e10 >= 0 ? dm * kPow10[e10] : dm / kPow10[-e10];     // one correctly rounded IEEE operation
   } else {
     slow[o] = 1;
-    valid[o] = 0;
-    out[o] = 0;
     return;
   }
   v = neg ? -v : v;
@@ -203,31 +211,51 @@ __global__ void __launch_bounds__(256) csv_parse_num_kernel(const uint8_t* __res
   valid[o] = 1;
 }
 
-// 64-bit FNV-1a of the unquoted field (""-escapes kept as written: equal strings hash equally), 0 for missing.
+// hash[o]: 64-bit FNV-1a of the cell's decoded bytes (a quoted field without its quotes, "" as one quote; any other
+// field as written), 0 for a missing cell (an NA string or empty). check[o]: a second hash of the same bytes with
+// another mixing function and the length folded in (0 for missing): cells of one hash[] value with different check[]
+// values are different strings. span[o] = the field's raw byte range, quotes included (the host decodes the
+// vocabulary from it by the same rule); (-1, -1) for a field that starts with a quote and is not a well-formed
+// quoted field (text after the closing quote, a single quote inside), which this reader does not parse.
 __global__ void __launch_bounds__(256) csv_hash_text_kernel(const uint8_t* __restrict__ buf,
                                                             const int64_t* __restrict__ fstart,
                                                             const int32_t* __restrict__ nfields, int64_t nrows,
                                                             int ncols, const int32_t* __restrict__ cols, int nout,
-                                                            uint64_t* __restrict__ hash, int64_t* __restrict__ span) {
+                                                            uint64_t* __restrict__ hash, int64_t* __restrict__ span,
+                                                            uint64_t* __restrict__ check) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nrows * nout) return;
   const int64_t r = i / nout;           // row-major as csv_parse_num: out[r * nout + j]
   const int j = (int)(i - r * nout);
   const int64_t o = i;
   int64_t a, b;
-  field_range(buf, fstart + r * (int64_t)(ncols + 1), nfields[r], cols[j], &a, &b);
-  span[2 * o] = a;
-  span[2 * o + 1] = b;
-  if (is_na(buf + a, (int)(b - a))) {
-    hash[o] = 0;
+  bool quoted;
+  field_value(buf, fstart + r * (int64_t)(ncols + 1), nfields[r], cols[j], &a, &b, &quoted);
+  span[2 * o] = quoted ? a - 1 : a;
+  span[2 * o + 1] = quoted ? b + 1 : b;
+  hash[o] = 0;
+  check[o] = 0;
+  if (is_na(buf + a, (int)min(b - a, (int64_t)9))) return;
+  bool odd = !quoted && buf[a] == '"';  // an opening quote without its closing quote at the field's end
+  uint64_t h = 14695981039346656037ull, g = 0x9E3779B97F4A7C15ull;
+  int64_t len = 0;
+  for (int64_t p = a; p < b; ++p, ++len) {
+    const uint8_t c = buf[p];
+    if (quoted && c == '"') {           // "" is one quote; a single quote inside a quoted field is not parsed
+      if (p + 1 < b && buf[p + 1] == '"') ++p;
+      else odd = true;
+    }
+    h ^= c;
+    h *= 1099511628211ull;
+    g = (g ^ c) * 0xFF51AFD7ED558CCDull;
+    g ^= g >> 32;
+  }
+  if (odd) {
+    span[2 * o] = span[2 * o + 1] = -1;
     return;
   }
-  uint64_t h = 1469598103934665603ull;
-  for (int64_t p = a; p < b; ++p) {
-    h ^= buf[p];
-    h *= 1099511628211ull;
-  }
   hash[o] = h ? h : 1;                  // 0 is reserved for missing
+  check[o] = g ^ (uint64_t)len;
 }
 
 }  // namespace
@@ -256,11 +284,11 @@ int tmog_hip_csv_parse_num(const uint8_t* buf, const int64_t* fstart, const int3
 
 int tmog_hip_csv_hash_text(const uint8_t* buf, const int64_t* fstart, const int32_t* nfields, int64_t nrows,
                            int ncols, const int32_t* cols, int nout, uint64_t* hash, int64_t* span,
-                           hipStream_t stream) {
+                           uint64_t* check, hipStream_t stream) {
   const int64_t n = nrows * (int64_t)nout;
   if (n <= 0) return 0;
   hipLaunchKernelGGL(csv_hash_text_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, buf, fstart,
-                     nfields, nrows, ncols, cols, nout, hash, span);
+                     nfields, nrows, ncols, cols, nout, hash, span, check);
   return (int)hipGetLastError();
 }
 

@@ -11,8 +11,11 @@ codes ordered by first appearance (``pandas.factorize`` semantics, as the Arrow 
 distinct strings' bytes come back to the host.
 
 Same dataset as :func:`readers.columnar.csv_dataset` (pyarrow): float64 reals, int64 integers, pandas' NA strings and
-empty cells missing, text codes by first appearance. Returns None when the file needs the generic path (a key
-function, extract functions, rows with a different field count, types the parser does not produce).
+empty cells missing, text codes by first appearance. A cell's value is pyarrow's: a field that starts and ends with a
+double quote is quoted (``""`` inside is one quote), any other field is literal -- text keeps its padding, numbers
+are parsed with spaces and tabs trimmed, in pyarrow's grammar. Returns None when the file needs the generic path (a
+key function, extract functions, rows with a different field count, a newline or a stray quote in a quoted field, a
+cell pyarrow would not convert, two strings with one hash, types the parser does not produce).
 """
 from __future__ import annotations
 
@@ -20,6 +23,7 @@ import concurrent.futures as cf
 import csv
 import io
 import os
+import re
 import time
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence
@@ -129,6 +133,7 @@ def gpu_csv_dataset(path: str, raw_features: Sequence, dev, names: Optional[Sequ
     num_ok: List[torch.Tensor] = []
     txt_hash: List[torch.Tensor] = []
     txt_span: List[torch.Tensor] = []
+    txt_check: List[torch.Tensor] = []
     prof = {"read_wait": 0.0, "loop": 0.0, "host_fix": 0.0, "sync": 0.0}
     fd = os.open(path, os.O_RDONLY)
 
@@ -184,7 +189,7 @@ def gpu_csv_dataset(path: str, raw_features: Sequence, dev, names: Optional[Sequ
                                prof, pending)
             if res is None:
                 return None
-            nv, ok, th, sp, pending = res
+            nv, ok, th, sp, ck, pending = res
             done = torch.cuda.Event()
             done.record(cur)
             dev_free[d] = done
@@ -193,6 +198,7 @@ def gpu_csv_dataset(path: str, raw_features: Sequence, dev, names: Optional[Sequ
             if th is not None:
                 txt_hash.append(th)
                 txt_span.append(sp)
+                txt_check.append(ck)
             i += 1
             if eof:
                 break
@@ -236,13 +242,20 @@ def gpu_csv_dataset(path: str, raw_features: Sequence, dev, names: Optional[Sequ
             v = R[pos[j]] if kind_of[c] == "real" else I[pos[j]]
             cols[c] = (v, None if all_ok[j] else OK[j])
     prof["finish_num"] = time.perf_counter() - t_fin
-    if txt_cols:
+    if txt_cols and n == 0:                 # no rows (a header-only file): empty columns
+        for c in txt_cols:
+            cols[c] = (torch.empty(0, dtype=torch.int32, device=dev), [])
+    elif txt_cols:
         Hh = torch.cat(txt_hash, 1) if len(txt_hash) > 1 else txt_hash[0]           # [nt, n]
         Sp = torch.cat(txt_span, 1) if len(txt_span) > 1 else txt_span[0]           # [nt, n, 2] file offsets
+        Ck = torch.cat(txt_check, 1) if len(txt_check) > 1 else txt_check[0]        # [nt, n]
         import mmap
         with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as mm:
             for j, c in enumerate(txt_cols):
-                codes, voc = _encode_hashes_spans(Hh[j], Sp[j], mm, dev)
+                enc = _encode_hashes_spans(Hh[j], Sp[j], mm, dev, Ck[j])
+                if enc is None:
+                    return None             # two strings with one hash: the generic path
+                codes, voc = enc
                 # a text feature whose cells all look like numbers is read as numbers and rendered back by the
                 # generic path (the Arrow path takes a text column only when Arrow types it as strings)
                 if c not in text_columns and voc and all(_numeric_literal(v) for v in voc):
@@ -287,10 +300,10 @@ def _check_pending(pending, N, prof) -> bool:
     device parser left to the host are parsed from the chunk's (still intact) host bytes."""
     h, fstart, flags, vals, ok, slow, nrows, ncol_t, kind_t = pending
     t0 = time.perf_counter()
-    f = flags.cpu().tolist()             # [ragged rows, slow cells]: one small read
+    f = flags.cpu().tolist()             # [ragged rows and unparsed quoted cells, slow cells]: one small read
     prof["sync"] += time.perf_counter() - t0
     if f[0]:
-        return False                    # ragged rows: pyarrow / pandas decide
+        return False                    # ragged rows, quoting this reader does not parse: pyarrow / pandas decide
     if f[1]:
         idx = torch.nonzero(slow.view(-1)).squeeze(1)
         t0 = time.perf_counter()
@@ -334,19 +347,47 @@ def _parse_chunk(lib, N, buf_all, h: _Host, end: int, final_nl: bool, ncols: int
                 "csv_parse_num")
     vals, ok, slow = vals_rm.t().contiguous(), ok_rm.t().contiguous(), slow_rm.t().contiguous()
     del vals_rm, ok_rm, slow_rm
-    th = sp = None
+    th = sp = ck = None
+    # rows with another field count, or ending inside quotes (nf = -1: a newline in a quoted field)
+    ragged = (nf != ncols).sum() if nrows else torch.zeros((), dtype=torch.int64, device=dev)
     if nt:
         th_rm = torch.empty(nrows, nt, dtype=torch.int64, device=dev)
         sp_rm = torch.empty(nrows, nt, 2, dtype=torch.int64, device=dev)
+        ck_rm = torch.empty(nrows, nt, dtype=torch.int64, device=dev)
         N.check(lib.tmog_hip_csv_hash_text(N.ptr(buf), N.ptr(fstart), N.ptr(nf), nrows, ncols, N.ptr(tcol_t), nt,
-                                           N.ptr(th_rm), N.ptr(sp_rm), st), "csv_hash_text")
+                                           N.ptr(th_rm), N.ptr(sp_rm), N.ptr(ck_rm), st), "csv_hash_text")
         th = th_rm.t().contiguous()
+        ck = ck_rm.t().contiguous()
         sp = sp_rm.transpose(0, 1).contiguous()
+        if nrows:                       # text cells whose quoting the kernel does not parse (span -1)
+            ragged = ragged + (sp[..., 0] < 0).sum()
         sp += h.base                    # chunk offsets -> file offsets (the bytes are re-read from the file)
-    ragged = (nf != ncols).sum() if nrows else torch.zeros((), dtype=torch.int64, device=dev)
     nslow = slow.sum(dtype=torch.int64) if nn and nrows else torch.zeros((), dtype=torch.int64, device=dev)
     flags = torch.stack([ragged.to(torch.int64), nslow])
-    return vals, ok, th, sp, (h, fstart, flags, vals, ok, slow, nrows, ncol_t, kind_t)
+    return vals, ok, th, sp, ck, (h, fstart, flags, vals, ok, slow, nrows, ncol_t, kind_t)
+
+
+# pyarrow's number grammar (after its trim of spaces and tabs): ASCII only, no "_", no hex
+_FLOAT_RE = re.compile(rb"[+-]?(?:(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?|[iI][nN][fF](?:[iI][nN][iI][tT][yY])?"
+                       rb"|[nN][aA][nN])")
+_INT_RE = re.compile(rb"-?[0-9]+")
+
+
+def _host_number(raw: bytes, integral: bool):
+    """``(int64 bits, valid)`` of a cell the device left to the host, or None where pyarrow's converter rejects it
+    (then the generic path decides). ``raw`` is the field as written; the NA strings were matched on the device."""
+    if len(raw) >= 2 and raw[:1] == b'"' and raw[-1:] == b'"':
+        raw = raw[1:-1]
+    raw = raw.strip(b" \t")
+    if integral:
+        if _INT_RE.fullmatch(raw) is None:
+            return None
+        v = int(raw)
+        return (v, 1) if -(1 << 63) <= v < (1 << 63) else None
+    if _FLOAT_RE.fullmatch(raw) is None:
+        return None
+    v = np.float64(float(raw))          # correctly rounded; beyond the double range: +-inf, as pyarrow
+    return int(v.view(np.int64)), 0 if np.isnan(v) else 1        # a NaN is missing (the Arrow path: notna)
 
 
 def _host_fix(h: _Host, fstart, vals, ok, idx, nrows, ncol_t, kind_t) -> bool:
@@ -359,19 +400,10 @@ def _host_fix(h: _Host, fstart, vals, ok, idx, nrows, ncol_t, kind_t) -> bool:
     out_ok = np.empty(len(idx), np.uint8)
     for t, (jj, rr) in enumerate(zip(j, r)):
         c = int(cols[jj])
-        s = h.np[fs[rr, c]:fs[rr, c + 1] - 1].tobytes().decode("utf-8", "replace").strip()
-        if len(s) >= 2 and s[0] == '"' and s[-1] == '"':
-            s = s[1:-1]
-        try:
-            if kinds[jj] == 1:
-                out_v[t] = int(s)
-            else:
-                out_v[t] = np.float64(float(s)).view(np.int64)
-            out_ok[t] = 1
-            if kinds[jj] == 0 and np.isnan(np.float64(float(s))):
-                out_ok[t] = 0               # a NaN is missing (the Arrow path: notna)
-        except ValueError:
+        got = _host_number(h.np[fs[rr, c]:fs[rr, c + 1] - 1].tobytes(), kinds[jj] == 1)
+        if got is None:
             return False                    # unparsable cell: the generic path reports it
+        out_v[t], out_ok[t] = got
     dev = vals.device
     vals.view(-1)[idx] = torch.as_tensor(out_v, device=dev)
     ok.view(-1)[idx] = torch.as_tensor(out_ok, device=dev)
@@ -386,17 +418,30 @@ def _numeric_literal(s: str) -> bool:
         return False
 
 
-def _encode_hashes_spans(h: torch.Tensor, span: torch.Tensor, mm, dev):
+def _decode_cell(raw: bytes) -> str:
+    """A text cell's string from the field as written (the rule of ``csv_hash_text``): quoted when it starts and
+    ends with a quote -- the quotes go and ``""`` is one quote -- literal otherwise."""
+    if len(raw) >= 2 and raw[:1] == b'"' and raw[-1:] == b'"':
+        raw = raw[1:-1].replace(b'""', b'"')
+    return raw.decode("utf-8", "replace")
+
+
+def _encode_hashes_spans(h: torch.Tensor, span: torch.Tensor, mm, dev, check: Optional[torch.Tensor] = None):
     """``(codes int32, vocab)`` from per-row 64-bit hashes (0 = missing) and the cells' file byte ranges: codes by
     first appearance; each distinct string read once from the file (memory-mapped) at its first cell. One stable
     sort: a group's first sorted position holds its first row (no scatter-min onto the few groups of a pick list,
-    whose atomics would contend on a handful of addresses)."""
+    whose atomics would contend on a handful of addresses). ``check`` is a second, independent hash per cell: two
+    cells of one hash with different ``check`` values are different strings, which one code cannot hold -- None."""
     n = int(h.numel())
     if n == 0:
         return torch.empty(0, dtype=torch.int32, device=dev), []
     hs, idx = torch.sort(h, stable=True)
     new = torch.ones(n, dtype=torch.bool, device=dev)
     new[1:] = hs[1:] != hs[:-1]
+    if check is not None and n > 1:
+        cs = check.index_select(0, idx)
+        if bool(((cs[1:] != cs[:-1]) & ~new[1:]).any()):
+            return None
     starts = torch.nonzero(new).squeeze(1)                  # first sorted position of every distinct hash
     gid = torch.cumsum(new.to(torch.int32), 0) - 1          # group of every sorted position
     first = idx.index_select(0, starts)                     # its first row (the sort is stable)
@@ -410,5 +455,5 @@ def _encode_hashes_spans(h: torch.Tensor, span: torch.Tensor, mm, dev):
     codes[idx] = grank.index_select(0, gid.long())
     rows = first.index_select(0, order[:n_used])
     spans = span.index_select(0, rows).cpu().numpy()
-    voc = [mm[a:b].decode("utf-8", "replace").replace('""', '"') for a, b in spans]
+    voc = [_decode_cell(mm[a:b]) for a, b in spans]
     return codes, voc
