@@ -9,7 +9,8 @@ semantics reproduced: quantile split candidates (``maxBins``), Poisson(1) bootst
 normalized leaf distributions, GBT log-loss boosting on {-1, +1} labels with ``1/(1+exp(-2F))``.
 XGBoost: second-order gain, ``min_child_weight``, ``lambda``, ``gamma`` post-pruning, ``eta``-scaled
 leaves, learned default direction for missing values (``missing`` = 0.0 by default in the
-reference grid), early stopping on the training ``aucpr``.
+reference grid), early stopping on the training ``aucpr``; the multiclass softmax objectives grow one tree
+per class and round (early stopping on the training ``merror`` / ``mlogloss``).
 
 Every (config x fold x tree) of a learner grows in the same level-synchronous forest; boosting
 learners advance all their models one round per engine call.
@@ -326,6 +327,10 @@ class _ForestLearner(Learner):
             state["_bins"] = BinSpec.from_state(state["bins"])
         return state["_forest"], state["_bins"]
 
+    def state_to_json(self, state):
+        # the decoded forest / bin objects cached by _forest() are not part of the checkpoint
+        return super().state_to_json({k: v for k, v in state.items() if not str(k).startswith("_")})
+
     def _binned(self, state, X, context):
         forest, spec = self._forest(state)
         if context is not None:
@@ -473,8 +478,9 @@ class DecisionTreeRegressorLearner(_ForestLearner):
 
 
 # -------------------------------------------------------------------------------- boosting
-def _boost_job_bytes(job, n_rows: int, n_features: int = 0, n_bins: int = 64) -> int:
-    """Device bytes one boosting job holds while its batch runs: its margin row (fp64) and (g, h) rows (fp32) over
+def _boost_job_bytes(job, n_rows: int, n_features: int = 0, n_bins: int = 64, n_pseudo: int = 1) -> int:
+    """Device bytes one boosting job holds while its batch runs (``n_pseudo`` times that for a model that grows
+    ``n_pseudo`` trees a round -- the classes of multiclass XGBoost): its margin row (fp64) and (g, h) rows (fp32) over
     the batch's rows; per training entry the grower's ping-pong entries and staged (g, h), the leaf assignment and
     the root packing (~40 bytes); and the grower's two level histograms -- F x (B + 1) x 2 statistics x 8 bytes
     for each node of the widest level (2^(max_depth - 1), at most one per training row), the size
@@ -483,7 +489,7 @@ def _boost_job_bytes(job, n_rows: int, n_features: int = 0, n_bins: int = 64) ->
     depth = int(job.params.get("max_depth", 6)) if getattr(job, "params", None) else 6
     nodes = min(1 << max(depth - 1, 0), max(n_train, 1))
     hist = 2 * n_features * (n_bins + 1) * 2 * 8 * nodes
-    return 16 * n_rows + 40 * n_train + hist
+    return max(1, int(n_pseudo)) * (16 * n_rows + 40 * n_train + hist)
 
 
 def _budget_chunks(job_bytes: Sequence[int], dev, frac: Optional[float] = None) -> List[tuple]:
@@ -518,6 +524,7 @@ class _BoostLearner(Learner):
     """Shared boosting loop: all jobs advance one round per engine call."""
     classification = True
     parallel = "features"       # every rank grows every tree over its feature slice
+    pseudo_jobs = 1             # trees a model grows per round (grower jobs and device rows it holds)
 
     def _rounds(self, p):
         raise NotImplementedError
@@ -547,7 +554,7 @@ class _BoostLearner(Learner):
                     NU = int(U.numel())
                     gjobs = [FitJob(j.params, r, j.weights) for j, r in zip(gjobs, parts)]
             res = []
-            for lo, hi in _budget_chunks([_boost_job_bytes(j, NU, F, key[0]) for j in gjobs], dev):
+            for lo, hi in _budget_chunks([_boost_job_bytes(j, NU, F, key[0], self.pseudo_jobs) for j in gjobs], dev):
                 res += self._boost(Xb, spec, yd, gjobs[lo:hi], NU, F, dev, key[0], par=_par(context))
             for k, i in enumerate(idxs):
                 out[i] = res[k]
@@ -562,13 +569,22 @@ class _BoostLearner(Learner):
             state["_bins"] = BinSpec.from_state(state["bins"])
         return state["_forest"], state["_bins"]
 
-    def margin(self, state, X, rows=None, context=None):
+    def state_to_json(self, state):
+        # the decoded forest / bin objects cached by _forest() are not part of the checkpoint
+        return super().state_to_json({k: v for k, v in state.items() if not str(k).startswith("_")})
+
+    def _binned_for(self, state, X, context):
+        """The model's forest and ``X`` binned as the model was trained."""
         forest, spec = self._forest(state)
         Xb = None
         if context is not None:
             Xb = _ctx(X, context).matching(spec)
         if Xb is None:
             Xb = quantize(X, spec)
+        return forest, Xb
+
+    def margin(self, state, X, rows=None, context=None):
+        forest, Xb = self._binned_for(state, X, context)
         m = TE.forest_predict(forest, Xb, [rows], [list(range(forest.n_trees))],
                               np.asarray(state["tree_weights"], np.float32))[0][:, 0].to(torch.float64)
         return m + float(state.get("base_margin", 0.0))
@@ -715,6 +731,55 @@ def _run_parts(dev, parts, fn):
         SP.release(dev, side)
 
 
+def _xgb_growth_matrix(Xb, spec, dev, par):
+    """The matrices the XGBoost learners hand to the grower, from the binned ``Xb``:
+    ``(Xg, n_bins_g, colperm, Xh, fp, csr, XgT)``."""
+    # Column order for growth: multi-bin columns first, then the one-present-bin ones (one-hot /
+    # null indicators), physically -- the histogram kernel's multi-bin groups then gather contiguous
+    # row bytes. It is the order the grower would use anyway (common/tree_grow.hpp), so trees are
+    # unchanged; split features are mapped back to the original columns after each round.
+    Xg, n_bins_g, colperm = Xb, spec.n_bins, None
+    if spec.missing_bin > 0 and os.environ.get("TMOG_XGB_COLPERM") != "0":
+        nb_all = np.asarray(spec.n_bins)
+        order = np.concatenate([np.nonzero(nb_all != 1)[0], np.nonzero(nb_all == 1)[0]])
+        if not np.array_equal(order, np.arange(nb_all.size)):
+            colperm = order.astype(np.int64)
+            Xg = Xb.index_select(1, torch.as_tensor(colperm, device=dev)).contiguous()
+            n_bins_g = nb_all[colperm]
+    # wide-load histogram items (tree_kernels.hip hist_wide_item) read 4 bins per lane with dword loads:
+    # pad the growth matrix to a dword row stride with columns that hold only the missing bin (one
+    # "present" bin that no row has: they can never split, and are mapped to column 0 if ever read)
+    if dev.type == "cuda" and spec.missing_bin > 0 and os.environ.get("TMOG_HIST_WIDE") != "0" \
+            and Xg.shape[1] % 4 != 0:
+        F0 = Xg.shape[1]
+        F4 = (F0 + 3) // 4 * 4
+        pad = torch.full((Xg.shape[0], F4 - F0), spec.missing_bin, dtype=Xg.dtype, device=dev)
+        Xg = torch.cat([Xg, pad], 1).contiguous()
+        n_bins_g = np.concatenate([np.asarray(n_bins_g), np.ones(F4 - F0, dtype=np.asarray(n_bins_g).dtype)])
+        base_perm = colperm if colperm is not None else np.arange(F0, dtype=np.int64)
+        colperm = np.concatenate([base_perm, np.zeros(F4 - F0, np.int64)])
+    # compact histogram matrix: the leading multi-bin columns of Xg at a 64-byte row stride (aligned row
+    # segments, and a footprint that fits the Infinity Cache better than the full padded rows); only the
+    # wide-load histogram items read it (tree_grow.hpp GrowArgs.Xh)
+    Xh = None
+    if dev.type == "cuda" and spec.missing_bin > 0 and os.environ.get("TMOG_HIST_COMPACT", "1") != "0":
+        nbg = np.asarray(n_bins_g)
+        n_multi = int(np.argmax(nbg == 1)) if (nbg == 1).any() else nbg.size
+        Fh = (n_multi + 63) // 64 * 64
+        if 0 < n_multi and Fh < Xg.shape[1] and (nbg[:n_multi] != 1).all():
+            Xh = Xg[:, :Fh].contiguous()
+    # feature-parallel over the ranks: this rank's slice of the growth-order feature lists
+    fp = TE.fp_plan(Xg, n_bins_g, par, sparse=spec.missing_bin >= 0) if par is not None else None
+    # one-hot / null-indicator columns: histogram from the rows' CSR lists (tree_kernels.hip)
+    csr = TE.onebin_csr(Xg, n_bins_g, cols=None if fp is None else fp.one_cols) \
+        if (dev.type == "cuda" and spec.missing_bin > 0) else None
+    # feature-major copy for the partition kernel's split-column reads (tree_grow.hpp GrowArgs.XbT)
+    XgT = Xg.t().contiguous() if (dev.type == "cuda" and os.environ.get("TMOG_PART_T", "1") != "0") else None
+    return Xg, n_bins_g, colperm, Xh, fp, csr, XgT
+
+
+MULTI_OBJECTIVES = ("multi:softprob", "multi:softmax")      # XGBoost's softmax objectives: one model
+
 # TMOG_XGB_PROFILE=1: per pipelined part, host seconds spent before / inside / after the native grower and in
 # the early-stopping read-back, printed to stderr after each XGBoost fit (diagnostics)
 _XGB_PROF: Optional[Dict[int, Dict[str, float]]] = {} if os.environ.get("TMOG_XGB_PROFILE") == "1" else None
@@ -722,12 +787,13 @@ _XGB_PROF: Optional[Dict[int, Dict[str, float]]] = {} if os.environ.get("TMOG_XG
 
 @register_learner
 class XGBoostClassifierLearner(_BoostLearner):
-    """Newton boosting with XGBoost semantics (binary:logistic)."""
+    """Newton boosting with XGBoost semantics: ``binary:logistic`` here, ``reg:squarederror`` and the multiclass
+    ``multi:softprob`` / ``multi:softmax`` through :meth:`fit_batch`."""
     name = "OpXGBoostClassifier"
     defaults = {"num_round": 100, "eta": 0.3, "gamma": 0.0, "max_depth": 6, "min_child_weight": 1.0,
                 "reg_lambda": 1.0, "missing": float("nan"), "max_bins": 64, "num_early_stopping_rounds": 0,
                 "eval_metric": "aucpr", "maximize_evaluation_metrics": True, "objective": "binary:logistic",
-                "base_score": 0.5, "subsample": 1.0, "colsample_bytree": 1.0, "seed": 0}
+                "base_score": 0.5, "subsample": 1.0, "colsample_bytree": 1.0, "seed": 0, "num_class": None}
 
     def _bin_key(self, p):
         miss = p.get("missing", float("nan"))
@@ -762,47 +828,7 @@ class XGBoostClassifierLearner(_BoostLearner):
         fused = dev.type == "cuda" and all(float(j.params.get("subsample", 1.0)) >= 1.0 for j in jobs) and \
             os.environ.get("TMOG_XGB_FUSED", "1") != "0"
         AUC_BINS = 1 << 16
-        # Column order for growth: multi-bin columns first, then the one-present-bin ones (one-hot /
-        # null indicators), physically -- the histogram kernel's multi-bin groups then gather contiguous
-        # row bytes. It is the order the grower would use anyway (common/tree_grow.hpp), so trees are
-        # unchanged; split features are mapped back to the original columns after each round.
-        Xg, n_bins_g, colperm = Xb, spec.n_bins, None
-        if spec.missing_bin > 0 and os.environ.get("TMOG_XGB_COLPERM") != "0":
-            nb_all = np.asarray(spec.n_bins)
-            order = np.concatenate([np.nonzero(nb_all != 1)[0], np.nonzero(nb_all == 1)[0]])
-            if not np.array_equal(order, np.arange(nb_all.size)):
-                colperm = order.astype(np.int64)
-                Xg = Xb.index_select(1, torch.as_tensor(colperm, device=dev)).contiguous()
-                n_bins_g = nb_all[colperm]
-        # wide-load histogram items (tree_kernels.hip hist_wide_item) read 4 bins per lane with dword loads:
-        # pad the growth matrix to a dword row stride with columns that hold only the missing bin (one
-        # "present" bin that no row has: they can never split, and are mapped to column 0 if ever read)
-        if dev.type == "cuda" and spec.missing_bin > 0 and os.environ.get("TMOG_HIST_WIDE") != "0" \
-                and Xg.shape[1] % 4 != 0:
-            F0 = Xg.shape[1]
-            F4 = (F0 + 3) // 4 * 4
-            pad = torch.full((Xg.shape[0], F4 - F0), spec.missing_bin, dtype=Xg.dtype, device=dev)
-            Xg = torch.cat([Xg, pad], 1).contiguous()
-            n_bins_g = np.concatenate([np.asarray(n_bins_g), np.ones(F4 - F0, dtype=np.asarray(n_bins_g).dtype)])
-            base_perm = colperm if colperm is not None else np.arange(F0, dtype=np.int64)
-            colperm = np.concatenate([base_perm, np.zeros(F4 - F0, np.int64)])
-        # compact histogram matrix: the leading multi-bin columns of Xg at a 64-byte row stride (aligned row
-        # segments, and a footprint that fits the Infinity Cache better than the full padded rows); only the
-        # wide-load histogram items read it (tree_grow.hpp GrowArgs.Xh)
-        Xh = None
-        if dev.type == "cuda" and spec.missing_bin > 0 and os.environ.get("TMOG_HIST_COMPACT", "1") != "0":
-            nbg = np.asarray(n_bins_g)
-            n_multi = int(np.argmax(nbg == 1)) if (nbg == 1).any() else nbg.size
-            Fh = (n_multi + 63) // 64 * 64
-            if 0 < n_multi and Fh < Xg.shape[1] and (nbg[:n_multi] != 1).all():
-                Xh = Xg[:, :Fh].contiguous()
-        # feature-parallel over the ranks: this rank's slice of the growth-order feature lists
-        fp = TE.fp_plan(Xg, n_bins_g, par, sparse=spec.missing_bin >= 0) if par is not None else None
-        # one-hot / null-indicator columns: histogram from the rows' CSR lists (tree_kernels.hip)
-        csr = TE.onebin_csr(Xg, n_bins_g, cols=None if fp is None else fp.one_cols) \
-            if (dev.type == "cuda" and spec.missing_bin > 0) else None
-        # feature-major copy for the partition kernel's split-column reads (tree_grow.hpp GrowArgs.XbT)
-        XgT = Xg.t().contiguous() if (dev.type == "cuda" and os.environ.get("TMOG_PART_T", "1") != "0") else None
+        Xg, n_bins_g, colperm, Xh, fp, csr, XgT = _xgb_growth_matrix(Xb, spec, dev, par)
         yf = yy.to(torch.float32).contiguous()
         G = H = None
         if fused:         # shared [P, N] statistics: each job's row is only touched by its own part
@@ -1045,21 +1071,52 @@ class XGBoostClassifierLearner(_BoostLearner):
         """Jobs with ``objective="reg:squarederror"`` (xgboost4j's own default, which a bare
         ``OpXGBoostClassifier`` in the reference trains with -- ``OpXGBoostClassifierTest.scala``; the model
         selector's grid sets ``binary:logistic``, ``DefaultSelectorParams.scala:72``) boost the label as a
-        regression target and score it as the class-1 probability."""
+        regression target and score it as the class-1 probability. Jobs with a multiclass objective go to
+        :class:`_SoftmaxXGBClassifier`; every other job keeps the binary path."""
         if type(self) is not XGBoostClassifierLearner:
             return super().fit_batch(X, y, jobs, context)
-        sq = [i for i, j in enumerate(jobs) if j.params.get("objective", "binary:logistic") == "reg:squarederror"]
-        if not sq:
+        obj = [j.params.get("objective", "binary:logistic") for j in jobs]
+        sq = [i for i, o in enumerate(obj) if o == "reg:squarederror"]
+        # multi:softprob / multi:softmax (the same model): K trees a round, grouped by the class count K --
+        # ``num_class`` if given, else max(label) + 1, at least 2
+        mc: Dict[int, List[int]] = {}
+        ymax = None
+        for i, o in enumerate(obj):
+            if o in MULTI_OBJECTIVES:
+                k = jobs[i].params.get("num_class")
+                if k is None:
+                    if ymax is None:
+                        ymax = int(y.max().item()) if y.numel() else 0
+                    k = ymax + 1
+                mc.setdefault(max(2, int(k)), []).append(i)
+        if not sq and not mc:
             return super().fit_batch(X, y, jobs, context)
-        lg = [i for i in range(len(jobs)) if i not in set(sq)]
+        other = set(sq).union(*mc.values())
+        lg = [i for i in range(len(jobs)) if i not in other]
         out = [None] * len(jobs)
         for i, r in zip(lg, super().fit_batch(X, y, [jobs[i] for i in lg], context) if lg else []):
             out[i] = r
-        for i, r in zip(sq, _SquaredErrorXGBClassifier().fit_batch(X, y, [jobs[i] for i in sq], context)):
+        for i, r in zip(sq, _SquaredErrorXGBClassifier().fit_batch(X, y, [jobs[i] for i in sq], context) if sq else []):
             out[i] = dict(r, objective="reg:squarederror")
+        for k, idxs in mc.items():
+            for i, r in zip(idxs, _SoftmaxXGBClassifier(k).fit_batch(X, y, [jobs[i] for i in idxs], context)):
+                out[i] = r
         return out
 
+    def margin(self, state, X, rows=None, context=None):
+        """``[n]`` margins; for a multiclass model ``[n, K]``: tree ``t`` belongs to class ``t % K``."""
+        if state.get("objective") not in MULTI_OBJECTIVES:
+            return super().margin(state, X, rows, context)
+        forest, Xb = self._binned_for(state, X, context)
+        K, T = int(state["n_classes"]), forest.n_trees
+        ms = TE.forest_predict(forest, Xb, [rows] * K, [list(range(k, T, K)) for k in range(K)],
+                               np.asarray(state["tree_weights"], np.float32))
+        return torch.stack([m[:, 0] for m in ms], 1).to(torch.float64) + float(state.get("base_margin", 0.0))
+
     def _outputs(self, state, m):
+        if m.dim() == 2:
+            prob = torch.softmax(m.to(torch.float64), 1)
+            return prob.argmax(1).to(torch.float64), m.to(torch.float64), prob
         if state.get("objective") == "reg:squarederror":
             # xgboost4j's binary model: raw = (-margin, margin), probability = (1 - p, p) with p the booster's
             # (identity-link) output, prediction from the probability
@@ -1077,6 +1134,229 @@ class _SquaredErrorXGBClassifier(XGBoostClassifierLearner):
 
     def _base_margin(self, bs):
         return float(bs)
+
+
+class _SoftmaxXGBClassifier(XGBoostClassifierLearner):
+    """Multiclass Newton boosting with XGBoost's softmax objective (``multi:softprob`` / ``multi:softmax``, see
+    :meth:`XGBoostClassifierLearner.fit_batch`); not registered.
+
+    A model with K classes grows K trees a round, one per class: K consecutive pseudo-jobs ``p * K + k`` of the
+    grower that share the model's rows and tree parameters (``G``, ``H`` and the margins are ``[P * K, N]``). What
+    couples them is the round epilogue: with ``p = softmax(margins)``, class k's next statistics are
+    ``g = p_k - [y == k]`` and ``h = max(2 p_k (1 - p_k), 1e-16)``. The base margin is ``base_score`` on every
+    class (it cancels in the softmax). Trees are stored round-major -- tree ``t`` belongs to class ``t % K`` -- and
+    early stopping (``merror``, the default, or ``mlogloss`` on the training rows, both minimised) keeps whole
+    rounds. (g, h) are zero outside a model's training rows, so their maxima over the training rows are the
+    maxima over all rows that the grower's fixed-point scales need.
+
+    On the GPU the epilogue is two launches (ops/csrc/hip/boost_multi_kernels.hip) and the trees grow on the
+    host-planned fused path: the device-resident level loop and the fused prologue take one maxima row and one
+    job per model, and are not used here."""
+
+    def __init__(self, n_classes: int, **params):
+        super().__init__(**params)
+        self.K = int(n_classes)
+        if not 2 <= self.K <= 64:
+            raise ValueError(f"multiclass XGBoost supports 2 to 64 classes, got {self.K}")
+
+    @property
+    def pseudo_jobs(self):
+        return self.K
+
+    def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None):
+        K = self.K
+        P = len(jobs)
+        Q = P * K
+        rows = [_rows(j, N, dev).to(torch.int64).contiguous() for j in jobs]
+        n_rows = [max(1, int(r.numel())) for r in rows]
+        rounds = [int(j.params.get("num_round", 100)) for j in jobs]
+        esr = [int(j.params.get("num_early_stopping_rounds", 0)) for j in jobs]
+        metric = []
+        for j in jobs:
+            em = j.params.get("eval_metric", "aucpr")
+            em = "merror" if em == "aucpr" else em          # the classifier's default metric is the binary one
+            if em not in ("merror", "mlogloss"):
+                raise ValueError(f"eval_metric {em} not supported for a multiclass objective")
+            metric.append(em)
+        base = [float(j.params.get("base_score", 0.5)) for j in jobs]
+        Fm = to_device(np.repeat(np.asarray(base, np.float64), K), dev, np.float64)[:, None].repeat(1, N)
+        yl = y.to(torch.int64)
+        yf = y.to(torch.float32).contiguous()
+        cls = torch.arange(K, device=dev)[:, None]
+        forests, weights = [[] for _ in range(P)], [[] for _ in range(P)]
+        best = [-float("inf")] * P
+        best_round = [0] * P
+        stopped = [False] * P
+        fused = dev.type == "cuda" and all(float(j.params.get("subsample", 1.0)) >= 1.0 for j in jobs) and \
+            os.environ.get("TMOG_XGB_FUSED", "1") != "0"
+        Xg, n_bins_g, colperm, Xh, fp, csr, XgT = _xgb_growth_matrix(Xb, spec, dev, par)
+        wide = TE.wide_rows(int(Xg.shape[0]))
+        # shared [P K, N] statistics: a model's K rows are only touched by the part that boosts the model
+        G = torch.zeros(Q, N, dtype=torch.float32, device=dev)
+        H = torch.zeros(Q, N, dtype=torch.float32, device=dev)
+        # the softmax kernel's per-pseudo-job maxima of (|g|, h) are the next round's quantisation maxima
+        # (TMOG_XGB_AMAX=0: the grower scans [P K, N] every round instead)
+        tam = amax_cur = None
+        if fused and os.environ.get("TMOG_XGB_AMAX", "1") != "0":
+            tam = torch.zeros(64, Q, 2, dtype=torch.int32, device=dev)      # boost_multi_kernels.hip kAmaxCopies
+            amax_cur = torch.zeros(Q, 2, dtype=torch.float32, device=dev)
+        es_lag = max(1, int(os.environ.get("TMOG_ES_LAG", "2"))) if fused else 1
+
+        def pseudo(ps):
+            return [p * K + k for p in ps for k in range(K)]
+
+        def grad_torch(ps):
+            """Reference epilogue in torch fp64: the models' (g, h) from their margins, on their rows."""
+            for p in ps:
+                r = rows[p]
+                pr = torch.softmax(Fm[p * K:(p + 1) * K].index_select(1, r), 0)
+                g = pr - (yl[r][None, :] == cls).to(torch.float64)
+                h = (2.0 * pr * (1.0 - pr)).clamp_min(1e-16)
+                G[p * K:(p + 1) * K].index_copy_(1, r, g.to(torch.float32))
+                H[p * K:(p + 1) * K].index_copy_(1, r, h.to(torch.float32))
+
+        def metric_torch(p):
+            m = Fm[p * K:(p + 1) * K].index_select(1, rows[p])
+            lab = yl[rows[p]]
+            if metric[p] == "merror":
+                return (m.argmax(0) != lab).to(torch.float64).sum() / n_rows[p]
+            return -torch.log_softmax(m, 0).gather(0, lab.clamp(0, K - 1)[None, :]).sum() / n_rows[p]
+
+        def run(ps, slot_base=0, groups=None):
+            """Boosting rounds of the models ``ps`` (all K pseudo-jobs of a model run in the same part: the softmax
+            reads all K margins; the trees do not depend on which other models grow alongside)."""
+            root_cache: Dict[tuple, tuple] = {}
+            lists: Dict[tuple, tuple] = {}
+            pending: list = []
+
+            def grad_fused(act, err):
+                key = tuple(act)
+                if key not in lists:
+                    lists.clear()
+                    off = np.concatenate([[0], np.cumsum([int(rows[p].numel()) for p in act])]).astype(np.int64)
+                    lists[key] = (torch.cat([rows[p] for p in act]), TE._const_tensor(off, dev),
+                                  TE._const_tensor(np.asarray(act, np.int64), dev),
+                                  max(int(rows[p].numel()) for p in act),
+                                  TE._const_tensor(np.asarray(pseudo(act), np.int64), dev))
+                cat, off_t, mod_t, longest, qi = lists[key]
+                if tam is not None:
+                    tam.index_fill_(1, qi, 0)
+                self._softmax_grad(cat, off_t, mod_t, len(act), longest, K, N, P, Fm, yf, G, H, tam, err)
+                if tam is not None:
+                    amax_cur.index_copy_(0, qi, tam.index_select(1, qi).view(torch.float32).amax(0))
+
+            def resolve(it0, need0, vals_t):
+                for p, v in zip(need0, vals_t.tolist()):
+                    if stopped[p]:
+                        continue
+                    if v > best[p] + 1e-12:
+                        best[p], best_round[p] = v, it0
+                    elif it0 - best_round[p] >= esr[p]:
+                        stopped[p] = True
+
+            if fused:
+                first = [p for p in ps if rounds[p] > 0]
+                if first:
+                    grad_fused(first, None)
+            for it in range(max([rounds[p] for p in ps], default=0)):
+                cancel.check()
+                act = [p for p in ps if it < rounds[p] and not stopped[p]]
+                if not act:
+                    break
+                if not fused:
+                    grad_torch(act)
+                tjobs = []
+                for p in act:
+                    pr = jobs[p].params
+                    tp = TE.TreeParams(max_depth=int(pr.get("max_depth", 6)),
+                                       min_child_weight=float(pr.get("min_child_weight", 1.0)),
+                                       reg_lambda=float(pr.get("reg_lambda", 1.0)), gamma=float(pr.get("gamma", 0.0)),
+                                       eta=float(pr.get("eta", 0.3)), split_eps=1e-6)
+                    w = None
+                    ss = float(pr.get("subsample", 1.0))
+                    if ss < 1.0:        # one row sample per model and round, shared by its K trees
+                        gen = torch.Generator().manual_seed(int(pr.get("seed", 0)) + 17 * it + p)
+                        w = (torch.rand(rows[p].numel(), generator=gen) < ss).to(torch.int64).to(dev)
+                    tjobs += [TE.TreeJob(p * K + k, tp, rows[p], w) for k in range(K)]
+                qact = pseudo(act)
+                root = None
+                if all(j.weights is None for j in tjobs):
+                    key = tuple(act)
+                    if key not in root_cache:
+                        root_cache.clear()
+                        root_cache[key] = TE._root_rows(tjobs, dev, wide)
+                    packed, cnts = root_cache[key]
+                    root = (packed.clone(), cnts)
+                forest = TE.grow_forest(Xg, n_bins_g, tjobs, mode=TE.MODE_GH, kind=TE.KIND_NEWTON, t1=G, t2=H, B=mb,
+                                        missing_bin=spec.missing_bin, collect_leaves=True, csr=csr, root=root, fp=fp,
+                                        slot_base=slot_base, groups=groups, XbT=XgT, quant_amax=amax_cur,
+                                        quant_wmax=1.0 if amax_cur is not None else None, Xh=Xh)
+                if colperm is not None:
+                    internal = forest.nodes[:, 2] >= 0
+                    forest.nodes[internal, 0] = colperm[forest.nodes[internal, 0]]
+                need = [p for p in act if esr[p] > 0]
+                err = None
+                if fused:
+                    self._margin_add(Fm, forest, qact, N)
+                    if any(metric[p] == "merror" for p in need):
+                        err = torch.zeros(P, dtype=torch.int32, device=dev)
+                    grad_fused(act, err)
+                else:
+                    _add_tree_margins(Fm, forest, Xb, qact, [1.0] * len(qact), tjobs)
+                for k_, q in enumerate(qact):        # round-major: class k's tree of this round at index it * K + k
+                    forests[q // K].append(forest.tree(k_))
+                    weights[q // K].append(1.0)
+                # early stopping on the training metric, read back es_lag rounds late (the final trim drops
+                # the trees grown meanwhile); both metrics are minimised: the negated value is maximised
+                if need:
+                    vals = [err[p].to(torch.float64) / n_rows[p] if (err is not None and metric[p] == "merror")
+                            else metric_torch(p) for p in need]
+                    while len(pending) >= es_lag:
+                        resolve(*pending.pop(0))
+                    pending.append((it, need, -torch.stack(vals)))
+            while pending:
+                resolve(*pending.pop(0))
+
+        parts = int(os.environ.get("TMOG_XGB_PIPE", "4"))
+        if fused and par is None and P >= 2 and parts >= 2:
+            # pipelined parts cut between models, never inside one
+            parts = min(parts, P)
+            cuts = np.linspace(0, P, parts + 1).astype(int)
+            gpp = max(1, int(os.environ.get("TMOG_XGB_PIPE_GROUPS", "1")))
+            _run_parts(dev, [(list(range(int(cuts[k]), int(cuts[k + 1]))), k * gpp, gpp) for k in range(parts)], run)
+        else:
+            run(list(range(P)))
+        res = []
+        for p in range(P):
+            keep = K * (len(forests[p]) // K if not stopped[p] else best_round[p] + 1)
+            res.append({"forest": TE.Forest.concat(forests[p][:keep]).to_state(), "bins": spec.to_state(),
+                        "tree_weights": np.asarray(weights[p][:keep], np.float32), "n_classes": K,
+                        "max_bins": mb, "base_margin": base[p], "num_trees": keep,
+                        "objective": str(jobs[p].params.get("objective", "multi:softprob"))})
+        return res
+
+    @staticmethod
+    def _margin_add(Fm, forest, qact, N):
+        """Margins of the round's pseudo-jobs += their trees' leaf values, from the leaf assignment."""
+        from ..ops import _native as NV
+        la = forest.leaf_assign
+        dev = Fm.device
+        val = la.value[:, 0].contiguous() if la.value.dim() == 2 else la.value.contiguous()
+        tree_job = TE._const_tensor(np.asarray(qact, np.int64), dev)
+        tree_c = la.tree.contiguous()
+        NV.check(NV.hip().tmog_hip_boost_margin_add(
+            NV.ptr(la.rows), NV.ptr(la.gid), int(la.rows.numel()), NV.ptr(val), NV.ptr(tree_c), NV.ptr(tree_job),
+            int(N), NV.ptr(Fm), int(val.shape[0]), len(qact), int(Fm.shape[0]), int(getattr(la, "wide", False)),
+            NV.stream(dev)), "boost_margin_add")
+
+    @staticmethod
+    def _softmax_grad(cat, off, models, M, longest, K, N, P, Fm, yf, G, H, tam, err):
+        """(g, h) of the ``M`` listed models on their training rows from the softmax of their margins, the
+        per-pseudo-job maxima into ``tam`` and (with ``err``) the per-model argmax error counts."""
+        from ..ops import _native as NV
+        NV.check(NV.hip().tmog_hip_softmax_grad(
+            NV.ptr(cat), NV.ptr(off), NV.ptr(models), int(M), int(longest), int(K), int(N), int(P), NV.ptr(Fm),
+            NV.ptr(yf), NV.ptr(G), NV.ptr(H), NV.ptr(tam), NV.ptr(err), NV.stream(Fm.device)), "softmax_grad")
 
 
 @register_learner

@@ -85,6 +85,8 @@ _HIP_SIGS = {
     "tmog_hip_zero_segments": [P, P, P, I32, I64, I64, I32, I32, P, I32, P],
     "tmog_hip_grow_timing": [P, I32],
     "tmog_hip_boost_epilogue": [P, P, I64, P, P, P, I64, P, P, P, P, I32, P, I32, I64, I64, I64, P, P, I32],
+    "tmog_hip_boost_margin_add": [P, P, I64, P, P, P, I64, P, I64, I64, I64, I32, P],
+    "tmog_hip_softmax_grad": [P, P, P, I32, I64, I32, I64, I64, P, P, P, P, P, P, P],
     "tmog_hip_aupr_counts": [P, I32, I32, P, P],
     "tmog_hip_slot_stream": [I32, P, I32],
     "tmog_hip_lr_blocks_per_cu": [I32],

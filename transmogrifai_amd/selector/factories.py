@@ -50,6 +50,7 @@ class DefaultSelectorParams:
     EarlyStopping = [20]
     MaximizeEvaluationMetrics = [True]
     BinaryClassXGBGamma = [0.8]
+    MultiClassXGBObjective = ["multi:softprob"]
 
 
 def param_grid(**axes) -> List[Dict]:
@@ -175,7 +176,12 @@ class MultiClassificationModelSelector(BinaryClassificationModelSelector):
     def models_and_params(cls):
         return {"OpLogisticRegression": _lr_grid(), "OpRandomForestClassifier": _rf_grid(D.ImpurityClass),
                 "OpNaiveBayes": param_grid(smoothing=D.NbSmoothing),
-                "OpDecisionTreeClassifier": _dt_grid(D.ImpurityClass)}
+                "OpDecisionTreeClassifier": _dt_grid(D.ImpurityClass),
+                # MultiClassificationModelSelector.scala:102-107 (off by default); the reference leaves the
+                # objective at xgboost4j's default, here the grid names the multiclass one
+                "OpXGBoostClassifier": param_grid(num_round=D.NumRound, eta=D.Eta, max_depth=D.MaxDepth,
+                                                  min_child_weight=D.MinChildWeight,
+                                                  objective=D.MultiClassXGBObjective)}
 
     @classmethod
     def with_cross_validation(cls, splitter="default", num_folds: int = 3, validation_metric=None,
