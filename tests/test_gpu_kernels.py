@@ -250,6 +250,40 @@ def test_aupr_counts_kernel_matches_torch():
     assert _native_loaded()
 
 
+@pytest.mark.parametrize("bins", [1, 2, 5, 1023, 1025])
+def test_aupr_counts_kernel_few_and_odd_bins(bins):
+    """One set with fewer bins than the workgroup has threads, with two-bin segments (1025) and with odd counts of
+    bins (the unaligned scalar loads)."""
+    from transmogrifai_amd.evaluators.metrics import _aupr_from_counts_torch, binned_aupr_from_counts
+    g = torch.Generator().manual_seed(70 + bins)
+    h = torch.randint(0, 4, (1, 2, bins), generator=g, dtype=torch.int32)
+    h[0, 1, bins // 2] = 3                                     # at least one positive
+    want = _aupr_from_counts_torch(h.double()).numpy()
+    got = binned_aupr_from_counts(h.cuda()).cpu().numpy()
+    np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-14)
+    assert want[0] > 0.0
+    assert _native_loaded()
+
+
+@pytest.mark.parametrize("bins", [5, 1025])
+def test_aupr_counts_kernel_cumulative_counts_beyond_int32(bins):
+    """Three positive bins of about 2^30 and two negative bins of 2^31 - 1: every bin fits int32, the running
+    (tp, fp) do not."""
+    from transmogrifai_amd.evaluators.metrics import _aupr_from_counts_torch, binned_aupr_from_counts
+    step = (bins - 1) // 4
+    h = torch.zeros(1, 2, bins, dtype=torch.int32)
+    for i, v in zip((0, 2, 4), ((1 << 30), (1 << 30) + 3, (1 << 30) - 5)):
+        h[0, 1, i * step] = v
+    for i in (1, 3):
+        h[0, 0, i * step] = (1 << 31) - 1
+    assert int(h.long().sum()) > (1 << 32)
+    want = _aupr_from_counts_torch(h.double()).numpy()
+    got = binned_aupr_from_counts(h.cuda()).cpu().numpy()
+    np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-14)
+    assert abs(want[0] - 0.5992) < 1e-3                        # the reference itself handles such a table
+    assert _native_loaded()
+
+
 def test_row_uniform_kernel_bit_identical():
     from transmogrifai_amd.tuning import splitters as SP
     rid = torch.randint(0, 1 << 40, (100_003,), dtype=torch.int64)
@@ -274,6 +308,31 @@ def test_poisson_pack_kernel_matches_host():
     assert (cc == (w > 0).sum(1).numpy()).all()
     off = np.concatenate([[0], np.cumsum(cc)])
     pg = pg.cpu()
+    for t in range(len(seeds)):
+        a, b = pc[off[t]:off[t + 1]], pg[off[t]:off[t + 1]]
+        assert torch.equal(a.sort().values, b.sort().values)
+    assert _native_loaded()
+
+
+@pytest.mark.parametrize("n,seeds,rate", [(20_000, [11, 12, 13], 0.05), (1, [11], 1.0), (1, [14], 0.05),
+                                          (63, [11], 1.0), (257, [12], 1.0), (257, [13], 0.05)])
+def test_poisson_pack_kernel_sparse_draws_and_short_lists(n, seeds, rate):
+    """A low rate drops most rows (whole waves, and the last block of 257 rows, keep nothing); row lists shorter
+    than a wave and one past a block; a single tree. Same order-free comparison as above."""
+    from transmogrifai_amd.models import tree_engine as TE
+    from transmogrifai_amd.models.trees import bootstrap_weights_multi
+    rows = torch.arange(3, 3 + 3 * n, 3, dtype=torch.int64)
+    pc, cc = TE.bootstrap_pack(rows, seeds, rate)
+    pg, cg = TE.bootstrap_pack(rows.cuda(), seeds, rate)
+    assert (cc == cg).all()
+    w = bootstrap_weights_multi(rows, seeds, rate)
+    assert (cc == (w > 0).sum(1).numpy()).all()
+    if rate < 0.5 and n > 1000:
+        keep = (w > 0)[:, : n // 64 * 64].view(len(seeds), -1, 64)
+        assert bool((keep.sum(2) == 0).any())                  # some wave keeps nothing
+    off = np.concatenate([[0], np.cumsum(cc)])
+    pg = pg.cpu()
+    assert pg.numel() == off[-1]
     for t in range(len(seeds)):
         a, b = pc[off[t]:off[t + 1]], pg[off[t]:off[t + 1]]
         assert torch.equal(a.sort().values, b.sort().values)

@@ -945,9 +945,13 @@ class XGBoostClassifierLearner(_BoostLearner):
                     if tam is not None and not prologue:
                         ai = TE._const_tensor(np.asarray(act, np.int64), dev)
                         tam.index_fill_(1, ai, 0)
-                    auc_counts = self._fused_epilogue(Fm, G, H, yf, forest, act, N,
-                                                      AUC_BINS if (need and self.classification) else 0,
-                                                      tam2[it & 1] if prologue else tam)
+                    # the kernel bins the sigmoid score of binary:logistic only: a squared-error classifier's
+                    # table would stay empty (AuPR 0 every round), so its early-stopping metric takes the torch
+                    # path below, from the same margins
+                    auc_counts = self._fused_epilogue(
+                        Fm, G, H, yf, forest, act, N,
+                        AUC_BINS if (need and self.classification and self.objective_code == 0) else 0,
+                        tam2[it & 1] if prologue else tam)
                     if tam is not None and not prologue:
                         amax_cur.index_copy_(0, ai, torch.maximum(
                             comp.index_select(0, ai), tam.index_select(1, ai).view(torch.float32).amax(0)))
