@@ -1,5 +1,6 @@
 """Multiclass XGBoost (``objective="multi:softprob"`` / ``"multi:softmax"``): K Newton trees a round coupled by the
-softmax round epilogue (models/trees.py ``_SoftmaxXGBClassifier``). CPU path = the torch fp64 epilogue."""
+softmax round epilogue (models/trees.py ``_SoftmaxObjective`` under ``_newton_boost``). CPU path = the torch fp64
+epilogue."""
 import json
 import os
 import socket

@@ -17,6 +17,7 @@ learners advance all their models one round per engine call.
 """
 from __future__ import annotations
 
+import functools
 import json
 import logging
 import math
@@ -189,10 +190,6 @@ def _add_tree_margins(Fm: torch.Tensor, forest: "TE.Forest", Xb, act: List[int],
     val = la.entry_value()[:, 0].to(torch.float64) * w_of[t]
     flat = Fm.view(-1)
     flat[idx] = flat[idx] + val
-
-
-def _model_rows_forest_predict(forest, Xb, rows_list, trees_list, tree_weight=None):
-    return TE.forest_predict(forest, Xb, rows_list, trees_list, tree_weight)
 
 
 # ------------------------------------------------------------------------------------ RF / DT
@@ -526,9 +523,6 @@ class _BoostLearner(Learner):
     parallel = "features"       # every rank grows every tree over its feature slice
     pseudo_jobs = 1             # trees a model grows per round (grower jobs and device rows it holds)
 
-    def _rounds(self, p):
-        raise NotImplementedError
-
     def fit_batch(self, X, y, jobs, context=None):
         if not jobs:
             return []
@@ -785,298 +779,498 @@ MULTI_OBJECTIVES = ("multi:softprob", "multi:softmax")      # XGBoost's softmax 
 _XGB_PROF: Optional[Dict[int, Dict[str, float]]] = {} if os.environ.get("TMOG_XGB_PROFILE") == "1" else None
 
 
-@register_learner
-class XGBoostClassifierLearner(_BoostLearner):
-    """Newton boosting with XGBoost semantics: ``binary:logistic`` here, ``reg:squarederror`` and the multiclass
-    ``multi:softprob`` / ``multi:softmax`` through :meth:`fit_batch`."""
-    name = "OpXGBoostClassifier"
-    defaults = {"num_round": 100, "eta": 0.3, "gamma": 0.0, "max_depth": 6, "min_child_weight": 1.0,
-                "reg_lambda": 1.0, "missing": float("nan"), "max_bins": 64, "num_early_stopping_rounds": 0,
-                "eval_metric": "aucpr", "maximize_evaluation_metrics": True, "objective": "binary:logistic",
-                "base_score": 0.5, "subsample": 1.0, "colsample_bytree": 1.0, "seed": 0, "num_class": None}
+class _PointwiseObjective:
+    """A Newton objective whose (g, h) of a row depend on that row's own margin: one tree per model and round,
+    ``Fm`` / ``G`` / ``H`` are ``[P, N]``. Subclasses give ``code``, ``grad`` and ``base_margin``. What an objective
+    supplies to the round driver is listed at :func:`_newton_boost`."""
+    K = 1                   # trees a model grows per round
+    n_classes = 2
+    code = 0                # boost_epilogue_kernel: 0 = binary:logistic, 1 = squared error
+    AUC_BINS = 1 << 16
 
-    def _bin_key(self, p):
-        miss = p.get("missing", float("nan"))
-        mv = None if (miss is None or (isinstance(miss, float) and math.isnan(miss))) else float(miss)
-        return (int(p.get("max_bins", 64)), mv, True)
-
-    def _grad(self, yy, Fm):
-        p = torch.sigmoid(Fm)
-        return p - yy, (p * (1 - p)).clamp_min(1e-16)
-
-    def _base_margin(self, bs):
-        bs = min(max(bs, 1e-12), 1 - 1e-12)
-        return math.log(bs / (1 - bs))
-
-    def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None):
-        from ..evaluators.metrics import binned_aupr_from_counts, binned_aupr_multi
-        t_setup0 = time.perf_counter()
+    def __init__(self, jobs, y, N, dev, fused, amax, resident, wide):
         P = len(jobs)
-        rows = [_rows(j, N, dev) for j in jobs]
-        rounds = [int(j.params.get("num_round", 100)) for j in jobs]
-        esr = [int(j.params.get("num_early_stopping_rounds", 0)) for j in jobs]
-        base = [self._base_margin(float(j.params.get("base_score", 0.5))) for j in jobs]
-        Fm = to_device(base, dev, np.float64)[:, None].repeat(1, N)
-        yy = y.to(torch.float64)
-        ylab = [yy[r] for r in rows]
-        forests, weights = [[] for _ in range(P)], [[] for _ in range(P)]
-        best = [-float("inf")] * P
-        best_round = [0] * P
-        stopped = [False] * P
-        # fused round epilogue on the device (ops/csrc/hip/boost_kernels.hip): margins, next gradients
-        # and the early-stopping AuPR counts in one launch per round instead of ~60 torch ops
-        fused = dev.type == "cuda" and all(float(j.params.get("subsample", 1.0)) >= 1.0 for j in jobs) and \
-            os.environ.get("TMOG_XGB_FUSED", "1") != "0"
-        AUC_BINS = 1 << 16
-        Xg, n_bins_g, colperm, Xh, fp, csr, XgT = _xgb_growth_matrix(Xb, spec, dev, par)
-        yf = yy.to(torch.float32).contiguous()
-        G = H = None
+        self.P, self.N, self.dev, self.fused, self.wide = P, N, dev, fused, wide
+        self.rows = rows = [_rows(j, N, dev) for j in jobs]
+        self.base = [self.base_margin(float(j.params.get("base_score", 0.5))) for j in jobs]
+        self.Fm = Fm = to_device(self.base, dev, np.float64)[:, None].repeat(1, N)
+        self.yy = yy = y.to(torch.float64)
+        self.ylab = [yy[r] for r in rows]
+        self.yf = yy.to(torch.float32).contiguous()
+        self.G = self.H = None
         if fused:         # shared [P, N] statistics: each job's row is only touched by its own part
-            G = torch.zeros(P, N, dtype=torch.float32, device=dev)
-            H = torch.zeros(P, N, dtype=torch.float32, device=dev)
-            for p in range(P):
-                if rounds[p] > 0:
-                    g, h = self._grad(yy, Fm[p])
+            self.G = G = torch.zeros(P, N, dtype=torch.float32, device=dev)
+            self.H = H = torch.zeros(P, N, dtype=torch.float32, device=dev)
+            for p, j in enumerate(jobs):
+                if int(j.params.get("num_round", 100)) > 0:
+                    g, h = self.grad(yy, Fm[p])
                     G[p], H[p] = g.to(torch.float32), h.to(torch.float32)
         # Quantisation maxima of the next round's (g, h) per job (tree_engine._quant_scales: max over all N
         # rows). Rows a job never trains on keep their round-0 statistics, so their max is taken once; the
         # round epilogue max-reduces the rows it rewrites -- no [P, N] scan per round.
-        amax_cur = comp = tam = None
-        if fused and os.environ.get("TMOG_XGB_AMAX", "1") != "0":
-            amax_cur = torch.stack([G.abs().amax(1), H.abs().amax(1)], 1).contiguous()
-            comp = torch.zeros(P, 2, dtype=torch.float32, device=dev)
+        self.amax_cur = self.comp = self.tam = None
+        if amax:
+            self.amax_cur = torch.stack([G.abs().amax(1), H.abs().amax(1)], 1).contiguous()
+            self.comp = comp = torch.zeros(P, 2, dtype=torch.float32, device=dev)
             for p in range(P):
                 out = torch.ones(N, dtype=torch.bool, device=dev)
                 out[rows[p]] = False
                 comp[p, 0] = torch.where(out, G[p].abs(), torch.zeros_like(G[p])).amax()
                 comp[p, 1] = torch.where(out, H[p].abs(), torch.zeros_like(H[p])).amax()
-            tam = torch.zeros(64, P, 2, dtype=torch.int32, device=dev)     # boost_kernels.hip kAmaxCopies
-
+            self.tam = torch.zeros(64, P, 2, dtype=torch.int32, device=dev)     # boost_kernels.hip kAmaxCopies
         # Device-planned trees (models/tree_engine.py resident=True, ops/csrc/hip/tree_resident.hip): on the fused
         # GPU path a round is enqueued without any host synchronisation -- the level plans, the tree finalisation
         # and the epilogue all run on the device; the host Forests are built from the node records once, after
         # the last round, and the early-stopping AuPR is read ES_LAG rounds late.
-        # a feature-parallel job (fp: the jobs spread over a rank group) grows on the device-planned loop too, as one
-        # job group whose level exchange (RCCL all-gather + merge of the split records) is enqueued on the stream
-        resident = fused and (par is None or fp is not None) and TE.resident_enabled()
-        es_lag = max(1, int(os.environ.get("TMOG_ES_LAG", "2"))) if resident else 1
+        self.resident = self.lagged = resident
         # Fused round prologue (tree_engine.boost_prologue): the scales, the root copy and the staged (g, h) in
         # one launch; the epilogue's maxima buffer is double-buffered (round it writes tam2[it & 1], which round
         # it's prologue zeroed; round it + 1's prologue reads it).
-        prologue = resident and tam is not None and P <= 64 and os.environ.get("TMOG_XGB_PROLOGUE", "1") != "0" \
-            and all(float(j.params.get("subsample", 1.0)) >= 1.0 for j in jobs)
-        tam2 = torch.zeros(2, 64, P, 2, dtype=torch.int32, device=dev) if prologue else None
+        self.prologue = resident and self.tam is not None and P <= 64 and \
+            os.environ.get("TMOG_XGB_PROLOGUE", "1") != "0"
+        self.tam2 = torch.zeros(2, 64, P, 2, dtype=torch.int32, device=dev) if self.prologue else None
 
-        def run(ps, slot_base=0, groups=None):
-            """Boosting rounds of the jobs ``ps`` (their trees do not depend on which other jobs grow
-            alongside: no per-node randomness, per-model quantisation, weights all 1 on this path)."""
-            nonlocal G, H
-            root_cache: Dict[tuple, tuple] = {}
-            prof = _XGB_PROF.setdefault(slot_base, {}) if _XGB_PROF is not None else None
-            tick = time.perf_counter
-            pending: list = []
-            deferred: list = []        # (act, ResidentTree) per device-planned round, in round order
-            pro_buf: dict = {}         # boost_prologue's reusable per-part buffers
+    def begin(self, ps):
+        return {}           # boost_prologue's reusable per-part buffers
 
-            def resolve(it0, need0, vals_t):
-                for p, v in zip(need0, vals_t.tolist()):
-                    if stopped[p]:
-                        continue
-                    if v > best[p] + 1e-12:
-                        best[p], best_round[p] = v, it0
-                    elif it0 - best_round[p] >= esr[p]:
-                        stopped[p] = True
+    def grad_torch(self, act):
+        self.G = G = torch.zeros(self.P, self.N, dtype=torch.float32, device=self.dev)
+        self.H = H = torch.zeros(self.P, self.N, dtype=torch.float32, device=self.dev)
+        for p in act:
+            g, h = self.grad(self.yy, self.Fm[p])
+            G[p], H[p] = g.to(torch.float32), h.to(torch.float32)
 
-            for it in range(max([rounds[p] for p in ps], default=0)):
-                cancel.check()
-                act = [p for p in ps if it < rounds[p] and not stopped[p]]
-                if not act:
-                    break
-                t_0 = tick()
-                if not fused:
-                    G = torch.zeros(P, N, dtype=torch.float32, device=dev)
-                    H = torch.zeros(P, N, dtype=torch.float32, device=dev)
-                    for p in act:
-                        g, h = self._grad(yy, Fm[p])
-                        G[p], H[p] = g.to(torch.float32), h.to(torch.float32)
-                tjobs = []
-                for p in act:
-                    pr = jobs[p].params
-                    tp = TE.TreeParams(max_depth=int(pr.get("max_depth", 6)),
-                                       min_child_weight=float(pr.get("min_child_weight", 1.0)),
-                                       reg_lambda=float(pr.get("reg_lambda", 1.0)), gamma=float(pr.get("gamma", 0.0)),
-                                       eta=float(pr.get("eta", 0.3)), split_eps=1e-6)
-                    r = rows[p]
-                    w = None
-                    ss = float(pr.get("subsample", 1.0))
-                    if ss < 1.0:
-                        gen = torch.Generator().manual_seed(int(pr.get("seed", 0)) + 17 * it + p)
-                        w = (torch.rand(r.numel(), generator=gen) < ss).to(torch.int64).to(dev)
-                    tjobs.append(TE.TreeJob(p, tp, r, w))
-                root = None
-                if all(j.weights is None for j in tjobs):
-                    # the packed root entries only change when a job stops: pack once per active set
-                    key = tuple(act)
-                    if key not in root_cache:
-                        root_cache.clear()
-                        root_cache[key] = TE._root_rows(tjobs, dev, TE.wide_rows(int(Xg.shape[0])))
-                    packed, cnts = root_cache[key]
-                    root = None if prologue else (packed.clone(), cnts)
-                pre = None
-                if prologue:
-                    pre = TE.boost_prologue(packed, cnts, act, G, H, amax_cur, comp,
-                                            tam2[(it - 1) & 1] if it > 0 else None, tam2[it & 1], pro_buf,
-                                            TE.wide_rows(int(Xg.shape[0])))
-                t_1 = tick()
-                forest = TE.grow_forest(Xg, n_bins_g, tjobs, mode=TE.MODE_GH, kind=TE.KIND_NEWTON, t1=G, t2=H, B=mb,
-                                        missing_bin=spec.missing_bin, collect_leaves=True, csr=csr, root=root, fp=fp,
-                                        slot_base=slot_base, groups=groups, XbT=XgT,
-                                        quant_amax=amax_cur, quant_wmax=1.0 if amax_cur is not None else None,
-                                        resident=resident and groups in (None, 1), prestaged=pre, Xh=Xh)
-                t_2 = tick()
-                is_res = isinstance(forest, TE.ResidentTree)
-                if colperm is not None and not is_res:
-                    internal = forest.nodes[:, 2] >= 0
-                    forest.nodes[internal, 0] = colperm[forest.nodes[internal, 0]]
-                need = [p for p in act if esr[p] > 0]
-                auc_counts = None
-                if fused:
-                    ai = None
-                    if tam is not None and not prologue:
-                        ai = TE._const_tensor(np.asarray(act, np.int64), dev)
-                        tam.index_fill_(1, ai, 0)
-                    # the kernel bins the sigmoid score of binary:logistic only: a squared-error classifier's
-                    # table would stay empty (AuPR 0 every round), so its early-stopping metric takes the torch
-                    # path below, from the same margins
-                    auc_counts = self._fused_epilogue(
-                        Fm, G, H, yf, forest, act, N,
-                        AUC_BINS if (need and self.classification and self.objective_code == 0) else 0,
-                        tam2[it & 1] if prologue else tam)
-                    if tam is not None and not prologue:
-                        amax_cur.index_copy_(0, ai, torch.maximum(
-                            comp.index_select(0, ai), tam.index_select(1, ai).view(torch.float32).amax(0)))
-                else:
-                    _add_tree_margins(Fm, forest, Xb, act, [1.0] * len(act), tjobs)
-                if is_res:
-                    deferred.append((list(act), forest))
-                    for p in act:
-                        forests[p].append(None)          # filled from the device records after the last round
-                        weights[p].append(1.0)
-                else:
-                    for k, p in enumerate(act):
-                        forests[p].append(forest.tree(k))
-                        weights[p].append(1.0)
-                t_3 = tick()
-                # early stopping on the training metric (the reference sets no eval set). The AuPR of round it
-                # is read back after round it + 1 has been grown, so the host never waits for a round's
-                # epilogue: a job that should stop after round it grows one extra tree, which the final
-                # trim (best_round + 1 trees) drops -- the same models as checking every round in step.
-                if need and self.classification:
-                    if auc_counts is not None:
-                        sel = auc_counts if len(need) == P else \
-                            auc_counts.index_select(0, TE._const_tensor(np.asarray(need, np.int64), dev))
-                        vals_t = binned_aupr_from_counts(sel)
-                    else:
-                        vals_t = binned_aupr_multi([torch.sigmoid(Fm[p][rows[p]]) for p in need],
-                                                   [ylab[p] for p in need])
-                    while len(pending) >= es_lag:
-                        resolve(*pending.pop(0))
-                    pending.append((it, need, vals_t))
-                if prof is not None:
-                    t_4 = tick()
-                    for k_, v_ in (("pre", t_1 - t_0), ("grow", t_2 - t_1), ("post", t_3 - t_2), ("es", t_4 - t_3)):
-                        prof[k_] = prof.get(k_, 0.0) + v_
-                    prof["rounds"] = prof.get("rounds", 0) + 1
-            while pending:
-                resolve(*pending.pop(0))
-            if deferred:
-                fs = TE.resident_forests([rt for _, rt in deferred])
-                cursor = {p: 0 for p in ps}
-                for (act_r, _), f in zip(deferred, fs):
-                    if colperm is not None:
-                        internal = f.nodes[:, 2] >= 0
-                        f.nodes[internal, 0] = colperm[f.nodes[internal, 0]]
-                    for k, p in enumerate(act_r):
-                        while forests[p][cursor[p]] is not None:
-                            cursor[p] += 1
-                        forests[p][cursor[p]] = f.tree(k)
+    def stage(self, it, act, packed, cnts, part):
+        tam2 = self.tam2
+        return TE.boost_prologue(packed, cnts, act, self.G, self.H, self.amax_cur, self.comp,
+                                 tam2[(it - 1) & 1] if it > 0 else None, tam2[it & 1], part, self.wide)
 
-        # Pipelined job parts (GPU, fused path): the jobs are split in two halves, each boosted by its
-        # own host thread on its own stream, so one half's per-round host work (tree finalisation,
-        # round set-up, the early-stopping read-back) overlaps the other half's kernels instead of
-        # idling the GPU. Trees are identical to the single-loop order (see run()).
-        parts = int(os.environ.get("TMOG_XGB_PIPE", "4"))
-        if _XGB_PROF is not None:
-            if dev.type == "cuda":
-                torch.cuda.synchronize(dev)
-            _XGB_PROF.setdefault("phases", {})["setup"] = time.perf_counter() - t_setup0
-            t_loop0 = time.perf_counter()
-        if fused and par is None and P >= 2 and parts >= 2:
-            parts = min(parts, P)
-            cuts = np.linspace(0, P, parts + 1).astype(int)
-            gpp = max(1, int(os.environ.get("TMOG_XGB_PIPE_GROUPS", "1")))
-            _run_parts(dev, [(list(range(int(cuts[k]), int(cuts[k + 1]))), k * gpp, gpp) for k in range(parts)], run)
-        else:
-            # feature-parallel: all jobs in one group on one stream (one communicator, one collective order)
-            run(list(range(P)), groups=1 if (resident and fp is not None) else None)
-        if _XGB_PROF is not None:
-            import sys as _sys
-            if dev.type == "cuda":
-                torch.cuda.synchronize(dev)
-            _XGB_PROF.setdefault("phases", {})["loop"] = time.perf_counter() - t_loop0
-            rep = {k: {a: round(b, 4) for a, b in v.items()} for k, v in _XGB_PROF.items()}
-            if dev.type == "cuda" and os.environ.get("TMOG_GROW_TIMING"):
-                from ..ops import _native as NV
-                tm = np.zeros(4, np.int64)
-                NV.hip().tmog_hip_grow_timing(tm.ctypes.data, 1)
-                rep["native"] = {"plan_s": tm[0] / 1e9, "issue_s": tm[1] / 1e9, "wait_s": tm[2] / 1e9,
-                                 "levels": int(tm[3])}
-            if dev.type == "cuda" and os.environ.get("TMOG_PLAN_PROFILE") == "1":
-                from ..ops import _native as NV
-                torch.cuda.synchronize(dev)
-                pp = np.zeros(32, np.uint64)
-                NV.hip().tmog_hip_plan_profile(pp.ctypes.data, 1)
-                calls = max(1, int(pp[31]))
-                # mean microseconds per level_plan_kernel call in each phase (100 MHz wall clock)
-                rep["plan_phase_us"] = {"calls": int(pp[31]),
-                                        **{str(k): round(float(pp[k]) / 100.0 / calls, 2) for k in range(12)}}
-            _sys.stderr.write("[xgb-profile] " + json.dumps(rep) + "\n")
-            _XGB_PROF.clear()
-        res = []
-        for p in range(P):
-            keep = len(forests[p]) if not stopped[p] else best_round[p] + 1
-            res.append({"forest": TE.Forest.concat(forests[p][:keep]).to_state(), "bins": spec.to_state(),
-                        "tree_weights": np.asarray(weights[p][:keep], np.float32), "n_classes": 2,
-                        "max_bins": mb, "base_margin": base[p], "num_trees": keep})
-        return res
-
-    objective_code = 0      # boost_epilogue_kernel: 0 = binary:logistic, 1 = squared error
-
-    def _fused_epilogue(self, Fm, G, H, yf, forest, act, N, bins, amax=None):
-        """Margins += this round's leaf values, next round's (g, h), and (with ``bins``) the per-job
+    def epilogue(self, it, act, qact, forest, need, part):
+        """Margins += this round's leaf values, next round's (g, h), and (for ``need``) the per-job
         (label, score-bin) counts of the new training scores, in one HIP launch."""
         from ..ops import _native as NV
+        dev, P, tam = self.dev, self.P, self.tam
+        ai = None
+        if tam is not None and not self.prologue:
+            ai = TE._const_tensor(np.asarray(act, np.int64), dev)
+            tam.index_fill_(1, ai, 0)
+        # the kernel bins the sigmoid score of binary:logistic only: a squared-error classifier's
+        # table would stay empty (AuPR 0 every round), so its early-stopping metric takes the torch
+        # path of metric(), from the same margins
+        bins = self.AUC_BINS if (need and self.code == 0) else 0
+        amax = self.tam2[it & 1] if self.prologue else tam
         la = forest.leaf_assign
-        dev = Fm.device
-        P = Fm.shape[0]
         counts = torch.zeros(P, 2, bins, dtype=torch.int32, device=dev) if bins else None
         val = la.value[:, 0].contiguous() if la.value.dim() == 2 else la.value.contiguous()
         tree_job = TE._const_tensor(np.asarray(act, np.int64), dev)
         tree_c = la.tree.contiguous()       # (bound: a temporary's block could be handed to the next allocation)
         NV.check(NV.hip().tmog_hip_boost_epilogue(
             NV.ptr(la.rows), NV.ptr(la.gid), int(la.rows.numel()), NV.ptr(val), NV.ptr(tree_c),
-            NV.ptr(tree_job), int(N), NV.ptr(Fm), NV.ptr(G), NV.ptr(H), NV.ptr(yf), self.objective_code,
-            NV.ptr(counts), int(bins), int(val.shape[0]), len(act), int(P), NV.stream(dev), NV.ptr(amax),
-            int(getattr(la, "wide", False))),
+            NV.ptr(tree_job), int(self.N), NV.ptr(self.Fm), NV.ptr(self.G), NV.ptr(self.H), NV.ptr(self.yf),
+            self.code, NV.ptr(counts), int(bins), int(val.shape[0]), len(act), int(P), NV.stream(dev),
+            NV.ptr(amax), int(getattr(la, "wide", False))),
             "boost_epilogue")
+        if ai is not None:
+            self.amax_cur.index_copy_(0, ai, torch.maximum(
+                self.comp.index_select(0, ai), tam.index_select(1, ai).view(torch.float32).amax(0)))
         return counts
+
+    def metric(self, need, counts):
+        """The training AuPR of the jobs ``need``, from the epilogue's counts or from the margins."""
+        from ..evaluators.metrics import binned_aupr_from_counts, binned_aupr_multi
+        if counts is not None:
+            return binned_aupr_from_counts(counts if len(need) == self.P else counts.index_select(
+                0, TE._const_tensor(np.asarray(need, np.int64), self.dev)))
+        return binned_aupr_multi([torch.sigmoid(self.Fm[p][self.rows[p]]) for p in need],
+                                 [self.ylab[p] for p in need])
+
+
+class _LogisticObjective(_PointwiseObjective):
+    """``binary:logistic``."""
+
+    @staticmethod
+    def grad(yy, Fm):
+        p = torch.sigmoid(Fm)
+        return p - yy, (p * (1 - p)).clamp_min(1e-16)
+
+    @staticmethod
+    def base_margin(bs):
+        bs = min(max(bs, 1e-12), 1 - 1e-12)
+        return math.log(bs / (1 - bs))
+
+
+class _SquaredErrorObjective(_PointwiseObjective):
+    """``reg:squarederror``, for the regressor and for the classifier that boosts a 0/1 label as a target."""
+    code = 1
+
+    @staticmethod
+    def grad(yy, Fm):
+        return Fm - yy, torch.ones_like(Fm)
+
+    @staticmethod
+    def base_margin(bs):
+        return float(bs)
+
+
+class _SoftmaxObjective:
+    """XGBoost's softmax objective (``multi:softprob`` / ``multi:softmax``) for :func:`_newton_boost`.
+
+    A model with K classes grows K trees a round, one per class: K consecutive pseudo-jobs ``p * K + k`` of the
+    grower that share the model's rows and tree parameters (``G``, ``H`` and the margins are ``[P * K, N]``). What
+    couples them is the round epilogue: with ``p = softmax(margins)``, class k's next statistics are
+    ``g = p_k - [y == k]`` and ``h = max(2 p_k (1 - p_k), 1e-16)``. The base margin is ``base_score`` on every
+    class (it cancels in the softmax). Early stopping reads ``merror`` (the default) or ``mlogloss`` on the
+    training rows, both minimised. (g, h) are zero outside a model's training rows, so their maxima over the
+    training rows are the maxima over all rows that the grower's fixed-point scales need.
+
+    On the GPU the epilogue is two launches (ops/csrc/hip/boost_multi_kernels.hip) and the trees grow on the
+    host-planned fused path: the device-resident level loop and the fused prologue take one maxima row and one
+    job per model, and are not used here."""
+    resident = prologue = False
+
+    def __init__(self, K, jobs, y, N, dev, fused, amax, resident, wide):
+        P = len(jobs)
+        Q = P * K
+        self.K = self.n_classes = K
+        self.P, self.N, self.dev = P, N, dev
+        self.rows = [_rows(j, N, dev).to(torch.int64).contiguous() for j in jobs]
+        self.n_rows = [max(1, int(r.numel())) for r in self.rows]
+        self.rounds = [int(j.params.get("num_round", 100)) for j in jobs]
+        self.metrics = []
+        for j in jobs:
+            em = j.params.get("eval_metric", "aucpr")
+            em = "merror" if em == "aucpr" else em          # the classifier's default metric is the binary one
+            if em not in ("merror", "mlogloss"):
+                raise ValueError(f"eval_metric {em} not supported for a multiclass objective")
+            self.metrics.append(em)
+        self.base = [float(j.params.get("base_score", 0.5)) for j in jobs]
+        self.Fm = to_device(np.repeat(np.asarray(self.base, np.float64), K), dev, np.float64)[:, None].repeat(1, N)
+        self.yl = y.to(torch.int64)
+        self.yf = y.to(torch.float32).contiguous()
+        self.cls = torch.arange(K, device=dev)[:, None]
+        # shared [P K, N] statistics: a model's K rows are only touched by the part that boosts the model
+        self.G = torch.zeros(Q, N, dtype=torch.float32, device=dev)
+        self.H = torch.zeros(Q, N, dtype=torch.float32, device=dev)
+        # the softmax kernel's per-pseudo-job maxima of (|g|, h) are the next round's quantisation maxima
+        # (TMOG_XGB_AMAX=0: the grower scans [P K, N] every round instead)
+        self.tam = self.amax_cur = None
+        if amax:
+            self.tam = torch.zeros(64, Q, 2, dtype=torch.int32, device=dev)     # boost_multi_kernels.hip kAmaxCopies
+            self.amax_cur = torch.zeros(Q, 2, dtype=torch.float32, device=dev)
+        self.fused = self.lagged = fused
+
+    def begin(self, ps):
+        """A part's cached row lists; on the fused path, after the statistics before round 0 of its models."""
+        part: Dict[tuple, tuple] = {}
+        first = [p for p in ps if self.rounds[p] > 0]
+        if self.fused and first:
+            self._grad_fused(first, None, part)
+        return part
+
+    def grad_torch(self, act):
+        """Reference epilogue in torch fp64: the models' (g, h) from their margins, on their rows."""
+        K = self.K
+        for p in act:
+            r = self.rows[p]
+            pr = torch.softmax(self.Fm[p * K:(p + 1) * K].index_select(1, r), 0)
+            g = pr - (self.yl[r][None, :] == self.cls).to(torch.float64)
+            h = (2.0 * pr * (1.0 - pr)).clamp_min(1e-16)
+            self.G[p * K:(p + 1) * K].index_copy_(1, r, g.to(torch.float32))
+            self.H[p * K:(p + 1) * K].index_copy_(1, r, h.to(torch.float32))
+
+    def _grad_fused(self, act, err, part):
+        rows, dev, K, tam = self.rows, self.dev, self.K, self.tam
+        key = tuple(act)
+        if key not in part:
+            part.clear()
+            off = np.concatenate([[0], np.cumsum([int(rows[p].numel()) for p in act])]).astype(np.int64)
+            part[key] = (torch.cat([rows[p] for p in act]), TE._const_tensor(off, dev),
+                         TE._const_tensor(np.asarray(act, np.int64), dev),
+                         max(int(rows[p].numel()) for p in act),
+                         TE._const_tensor(np.asarray([p * K + k for p in act for k in range(K)], np.int64), dev))
+        cat, off_t, mod_t, longest, qi = part[key]
+        if tam is not None:
+            tam.index_fill_(1, qi, 0)
+        self._softmax_grad(cat, off_t, mod_t, len(act), longest, K, self.N, self.P, self.Fm, self.yf, self.G,
+                           self.H, tam, err)
+        if tam is not None:
+            self.amax_cur.index_copy_(0, qi, tam.index_select(1, qi).view(torch.float32).amax(0))
+
+    def epilogue(self, it, act, qact, forest, need, part):
+        """Margins += this round's leaf values, then the softmax (g, h); returns the per-model argmax error
+        counts if a job of ``need`` stops on ``merror``."""
+        self._margin_add(self.Fm, forest, qact, self.N)
+        err = None
+        if any(self.metrics[p] == "merror" for p in need):
+            err = torch.zeros(self.P, dtype=torch.int32, device=self.dev)
+        self._grad_fused(act, err, part)
+        return err
+
+    def metric(self, need, err):
+        """Both metrics are minimised: the negated value is maximised."""
+        return -torch.stack([err[p].to(torch.float64) / self.n_rows[p]
+                             if (err is not None and self.metrics[p] == "merror") else self._metric_torch(p)
+                             for p in need])
+
+    def _metric_torch(self, p):
+        K = self.K
+        m = self.Fm[p * K:(p + 1) * K].index_select(1, self.rows[p])
+        lab = self.yl[self.rows[p]]
+        if self.metrics[p] == "merror":
+            return (m.argmax(0) != lab).to(torch.float64).sum() / self.n_rows[p]
+        return -torch.log_softmax(m, 0).gather(0, lab.clamp(0, K - 1)[None, :]).sum() / self.n_rows[p]
+
+    @staticmethod
+    def _margin_add(Fm, forest, qact, N):
+        """Margins of the round's pseudo-jobs += their trees' leaf values, from the leaf assignment."""
+        from ..ops import _native as NV
+        la = forest.leaf_assign
+        dev = Fm.device
+        val = la.value[:, 0].contiguous() if la.value.dim() == 2 else la.value.contiguous()
+        tree_job = TE._const_tensor(np.asarray(qact, np.int64), dev)
+        tree_c = la.tree.contiguous()
+        NV.check(NV.hip().tmog_hip_boost_margin_add(
+            NV.ptr(la.rows), NV.ptr(la.gid), int(la.rows.numel()), NV.ptr(val), NV.ptr(tree_c), NV.ptr(tree_job),
+            int(N), NV.ptr(Fm), int(val.shape[0]), len(qact), int(Fm.shape[0]), int(getattr(la, "wide", False)),
+            NV.stream(dev)), "boost_margin_add")
+
+    @staticmethod
+    def _softmax_grad(cat, off, models, M, longest, K, N, P, Fm, yf, G, H, tam, err):
+        """(g, h) of the ``M`` listed models on their training rows from the softmax of their margins, the
+        per-pseudo-job maxima into ``tam`` and (with ``err``) the per-model argmax error counts."""
+        from ..ops import _native as NV
+        NV.check(NV.hip().tmog_hip_softmax_grad(
+            NV.ptr(cat), NV.ptr(off), NV.ptr(models), int(M), int(longest), int(K), int(N), int(P), NV.ptr(Fm),
+            NV.ptr(yf), NV.ptr(G), NV.ptr(H), NV.ptr(tam), NV.ptr(err), NV.stream(Fm.device)), "softmax_grad")
+
+
+def _remap_features(forest, colperm):
+    """Split features of trees grown on the reordered growth matrix, back to the original columns."""
+    if colperm is not None:
+        internal = forest.nodes[:, 2] >= 0
+        forest.nodes[internal, 0] = colperm[forest.nodes[internal, 0]]
+
+
+def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb, par=None):
+    """The boosting rounds of every XGBoost learner: the states of ``jobs``, all advanced one round per grower call.
+
+    ``make_objective(jobs, y, N, dev, fused=, amax=, resident=, wide=)`` builds what differs between objectives:
+    ``K`` trees per model and round (model ``p`` is the grower's pseudo-jobs ``p * K + k``), the models' ``rows``
+    and ``base`` margins, the margins ``Fm`` and statistics ``G`` / ``H`` (``[P K, N]``, with the statistics before
+    round 0 on the fused path), the quantisation maxima ``amax_cur``, and whether it runs on the device-planned loop
+    (``resident``), with the fused prologue (``prologue``, then ``stage()`` returns grow_forest's ``prestaged``) and
+    with a lagged early-stopping read-back (``lagged``). Per part it gives ``begin(ps)`` (its scratch); per round
+    ``grad_torch(act)`` before growth on the torch path, ``epilogue(...)`` after growth on the fused path (margins,
+    next statistics, maxima) and ``metric(need, aux)``: the early-stopping values, larger is better."""
+    t_setup0 = time.perf_counter()
+    P = len(jobs)
+    rounds = [int(j.params.get("num_round", 100)) for j in jobs]
+    esr = [int(j.params.get("num_early_stopping_rounds", 0)) if early_stopping else 0 for j in jobs]
+    forests, weights = [[] for _ in range(P)], [[] for _ in range(P)]
+    best = [-float("inf")] * P
+    best_round = [0] * P
+    stopped = [False] * P
+    # fused round epilogue on the device (ops/csrc/hip/boost_kernels.hip, boost_multi_kernels.hip): margins, next
+    # gradients and the early-stopping counts in one or two launches per round instead of ~60 torch ops
+    fused = dev.type == "cuda" and all(float(j.params.get("subsample", 1.0)) >= 1.0 for j in jobs) and \
+        os.environ.get("TMOG_XGB_FUSED", "1") != "0"
+    Xg, n_bins_g, colperm, Xh, fp, csr, XgT = _xgb_growth_matrix(Xb, spec, dev, par)
+    wide = TE.wide_rows(int(Xg.shape[0]))
+    # a feature-parallel job (fp: the jobs spread over a rank group) grows on the device-planned loop too, as one
+    # job group whose level exchange (RCCL all-gather + merge of the split records) is enqueued on the stream
+    obj = make_objective(jobs, y, N, dev, fused=fused, amax=fused and os.environ.get("TMOG_XGB_AMAX", "1") != "0",
+                         resident=fused and (par is None or fp is not None) and TE.resident_enabled(), wide=wide)
+    K, rows, Fm, amax_cur = obj.K, obj.rows, obj.Fm, obj.amax_cur
+    resident, prologue = obj.resident, obj.prologue
+    es_lag = max(1, int(os.environ.get("TMOG_ES_LAG", "2"))) if obj.lagged else 1
+
+    def run(ps, slot_base=0, groups=None):
+        """Boosting rounds of the models ``ps`` (all K pseudo-jobs of a model run in the same part; the trees do not
+        depend on which other models grow alongside: no per-node randomness, per-model quantisation, weights all 1
+        on the pipelined path)."""
+        root_cache: Dict[tuple, tuple] = {}
+        prof = _XGB_PROF.setdefault(slot_base, {}) if _XGB_PROF is not None else None
+        tick = time.perf_counter
+        pending: list = []
+        deferred: list = []        # (pseudo-jobs, ResidentTree) per device-planned round, in round order
+        part = obj.begin(ps)
+
+        def resolve(it0, need0, vals_t):
+            for p, v in zip(need0, vals_t.tolist()):
+                if stopped[p]:
+                    continue
+                if v > best[p] + 1e-12:
+                    best[p], best_round[p] = v, it0
+                elif it0 - best_round[p] >= esr[p]:
+                    stopped[p] = True
+
+        for it in range(max([rounds[p] for p in ps], default=0)):
+            cancel.check()
+            act = [p for p in ps if it < rounds[p] and not stopped[p]]
+            if not act:
+                break
+            t_0 = tick()
+            if not fused:
+                obj.grad_torch(act)
+            tjobs = []
+            for p in act:
+                pr = jobs[p].params
+                tp = TE.TreeParams(max_depth=int(pr.get("max_depth", 6)),
+                                   min_child_weight=float(pr.get("min_child_weight", 1.0)),
+                                   reg_lambda=float(pr.get("reg_lambda", 1.0)), gamma=float(pr.get("gamma", 0.0)),
+                                   eta=float(pr.get("eta", 0.3)), split_eps=1e-6)
+                w = None
+                ss = float(pr.get("subsample", 1.0))
+                if ss < 1.0:        # one row sample per model and round, shared by its K trees
+                    gen = torch.Generator().manual_seed(int(pr.get("seed", 0)) + 17 * it + p)
+                    w = (torch.rand(rows[p].numel(), generator=gen) < ss).to(torch.int64).to(dev)
+                tjobs += [TE.TreeJob(p * K + k, tp, rows[p], w) for k in range(K)]
+            qact = [j.model for j in tjobs]
+            root = pre = None
+            if all(j.weights is None for j in tjobs):
+                # the packed root entries only change when a job stops: pack once per active set
+                key = tuple(act)
+                if key not in root_cache:
+                    root_cache.clear()
+                    root_cache[key] = TE._root_rows(tjobs, dev, wide)
+                packed, cnts = root_cache[key]
+                if prologue:
+                    pre = obj.stage(it, act, packed, cnts, part)
+                else:
+                    root = (packed.clone(), cnts)
+            t_1 = tick()
+            forest = TE.grow_forest(Xg, n_bins_g, tjobs, mode=TE.MODE_GH, kind=TE.KIND_NEWTON, t1=obj.G, t2=obj.H,
+                                    B=mb, missing_bin=spec.missing_bin, collect_leaves=True, csr=csr, root=root,
+                                    fp=fp, slot_base=slot_base, groups=groups, XbT=XgT,
+                                    quant_amax=amax_cur, quant_wmax=1.0 if amax_cur is not None else None,
+                                    resident=resident and groups in (None, 1), prestaged=pre, Xh=Xh)
+            t_2 = tick()
+            is_res = isinstance(forest, TE.ResidentTree)
+            if not is_res:
+                _remap_features(forest, colperm)
+            need = [p for p in act if esr[p] > 0]
+            aux = None
+            if fused:
+                aux = obj.epilogue(it, act, qact, forest, need, part)
+            else:
+                _add_tree_margins(Fm, forest, Xb, qact, [1.0] * len(qact), tjobs)
+            if is_res:
+                deferred.append((qact, forest))
+            # round-major: class k's tree of this round at index it * K + k; a device-planned round's trees are
+            # filled from the device records after the last round
+            for k_, q in enumerate(qact):
+                forests[q // K].append(None if is_res else forest.tree(k_))
+                weights[q // K].append(1.0)
+            t_3 = tick()
+            # early stopping on the training metric (the reference sets no eval set). The metric of round it
+            # is read back after round it + es_lag has been grown, so the host never waits for a round's
+            # epilogue: a job that should stop after round it grows extra trees, which the final
+            # trim (best_round + 1 rounds) drops -- the same models as checking every round in step.
+            if need:
+                vals_t = obj.metric(need, aux)
+                while len(pending) >= es_lag:
+                    resolve(*pending.pop(0))
+                pending.append((it, need, vals_t))
+            if prof is not None:
+                t_4 = tick()
+                for k_, v_ in (("pre", t_1 - t_0), ("grow", t_2 - t_1), ("post", t_3 - t_2), ("es", t_4 - t_3)):
+                    prof[k_] = prof.get(k_, 0.0) + v_
+                prof["rounds"] = prof.get("rounds", 0) + 1
+        while pending:
+            resolve(*pending.pop(0))
+        if deferred:
+            fs = TE.resident_forests([rt for _, rt in deferred])
+            cursor = {p: 0 for p in ps}
+            for (qact_r, _), f in zip(deferred, fs):
+                _remap_features(f, colperm)
+                for k_, q in enumerate(qact_r):
+                    p = q // K
+                    while forests[p][cursor[p]] is not None:
+                        cursor[p] += 1
+                    forests[p][cursor[p]] = f.tree(k_)
+
+    # Pipelined job parts (GPU, fused path): the models are split into parts (cut between models, never inside
+    # one), each boosted by its own host thread on its own stream, so one part's per-round host work (tree
+    # finalisation, round set-up, the early-stopping read-back) overlaps the other parts' kernels instead of
+    # idling the GPU. Trees are identical to the single-loop order (see run()).
+    parts = int(os.environ.get("TMOG_XGB_PIPE", "4"))
+    if _XGB_PROF is not None:
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        _XGB_PROF.setdefault("phases", {})["setup"] = time.perf_counter() - t_setup0
+        t_loop0 = time.perf_counter()
+    if fused and par is None and P >= 2 and parts >= 2:
+        parts = min(parts, P)
+        cuts = np.linspace(0, P, parts + 1).astype(int)
+        gpp = max(1, int(os.environ.get("TMOG_XGB_PIPE_GROUPS", "1")))
+        _run_parts(dev, [(list(range(int(cuts[k]), int(cuts[k + 1]))), k * gpp, gpp) for k in range(parts)], run)
+    else:
+        # feature-parallel: all jobs in one group on one stream (one communicator, one collective order)
+        run(list(range(P)), groups=1 if (resident and fp is not None) else None)
+    if _XGB_PROF is not None:
+        _xgb_profile_report(dev, t_loop0)
+    res = []
+    for p in range(P):
+        keep = K * (len(forests[p]) // K if not stopped[p] else best_round[p] + 1)
+        res.append({"forest": TE.Forest.concat(forests[p][:keep]).to_state(), "bins": spec.to_state(),
+                    "tree_weights": np.asarray(weights[p][:keep], np.float32), "n_classes": obj.n_classes,
+                    "max_bins": mb, "base_margin": obj.base[p], "num_trees": keep})
+    return res
+
+
+def _xgb_profile_report(dev, t_loop0):
+    """Print and reset the ``TMOG_XGB_PROFILE`` figures of one fit."""
+    import sys as _sys
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    _XGB_PROF.setdefault("phases", {})["loop"] = time.perf_counter() - t_loop0
+    rep = {k: {a: round(b, 4) for a, b in v.items()} for k, v in _XGB_PROF.items()}
+    if dev.type == "cuda" and os.environ.get("TMOG_GROW_TIMING"):
+        from ..ops import _native as NV
+        tm = np.zeros(4, np.int64)
+        NV.hip().tmog_hip_grow_timing(tm.ctypes.data, 1)
+        rep["native"] = {"plan_s": tm[0] / 1e9, "issue_s": tm[1] / 1e9, "wait_s": tm[2] / 1e9,
+                         "levels": int(tm[3])}
+    if dev.type == "cuda" and os.environ.get("TMOG_PLAN_PROFILE") == "1":
+        from ..ops import _native as NV
+        torch.cuda.synchronize(dev)
+        pp = np.zeros(32, np.uint64)
+        NV.hip().tmog_hip_plan_profile(pp.ctypes.data, 1)
+        calls = max(1, int(pp[31]))
+        # mean microseconds per level_plan_kernel call in each phase (100 MHz wall clock)
+        rep["plan_phase_us"] = {"calls": int(pp[31]),
+                                **{str(k): round(float(pp[k]) / 100.0 / calls, 2) for k in range(12)}}
+    _sys.stderr.write("[xgb-profile] " + json.dumps(rep) + "\n")
+    _XGB_PROF.clear()
+
+
+@register_learner
+class XGBoostClassifierLearner(_BoostLearner):
+    """Newton boosting with XGBoost semantics: ``binary:logistic`` here, ``reg:squarederror`` and the multiclass
+    ``multi:softprob`` / ``multi:softmax`` through :meth:`fit_batch`. Every objective runs the rounds of
+    :func:`_newton_boost`."""
+    name = "OpXGBoostClassifier"
+    defaults = {"num_round": 100, "eta": 0.3, "gamma": 0.0, "max_depth": 6, "min_child_weight": 1.0,
+                "reg_lambda": 1.0, "missing": float("nan"), "max_bins": 64, "num_early_stopping_rounds": 0,
+                "eval_metric": "aucpr", "maximize_evaluation_metrics": True, "objective": "binary:logistic",
+                "base_score": 0.5, "subsample": 1.0, "colsample_bytree": 1.0, "seed": 0, "num_class": None}
+    _objective = _LogisticObjective
+
+    def _bin_key(self, p):
+        miss = p.get("missing", float("nan"))
+        mv = None if (miss is None or (isinstance(miss, float) and math.isnan(miss))) else float(miss)
+        return (int(p.get("max_bins", 64)), mv, True)
+
+    def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None):
+        # early stopping (on the training metric) is the classifiers': the regressor grows all its rounds
+        return _newton_boost(self._objective, self.classification, Xb, spec, y, jobs, N, dev, mb, par)
 
     def fit_batch(self, X, y, jobs, context=None):
         """Jobs with ``objective="reg:squarederror"`` (xgboost4j's own default, which a bare
         ``OpXGBoostClassifier`` in the reference trains with -- ``OpXGBoostClassifierTest.scala``; the model
         selector's grid sets ``binary:logistic``, ``DefaultSelectorParams.scala:72``) boost the label as a
         regression target and score it as the class-1 probability. Jobs with a multiclass objective go to
-        :class:`_SoftmaxXGBClassifier`; every other job keeps the binary path."""
+        :class:`_SoftmaxXGBClassifier`; every other job keeps the binary objective."""
         if type(self) is not XGBoostClassifierLearner:
             return super().fit_batch(X, y, jobs, context)
         obj = [j.params.get("objective", "binary:logistic") for j in jobs]
@@ -1131,31 +1325,13 @@ class XGBoostClassifierLearner(_BoostLearner):
 
 class _SquaredErrorXGBClassifier(XGBoostClassifierLearner):
     """Squared-error boosting of a 0/1 label (see :meth:`XGBoostClassifierLearner.fit_batch`); not registered."""
-    objective_code = 1
-
-    def _grad(self, yy, Fm):
-        return Fm - yy, torch.ones_like(Fm)
-
-    def _base_margin(self, bs):
-        return float(bs)
+    _objective = _SquaredErrorObjective
 
 
 class _SoftmaxXGBClassifier(XGBoostClassifierLearner):
-    """Multiclass Newton boosting with XGBoost's softmax objective (``multi:softprob`` / ``multi:softmax``, see
-    :meth:`XGBoostClassifierLearner.fit_batch`); not registered.
-
-    A model with K classes grows K trees a round, one per class: K consecutive pseudo-jobs ``p * K + k`` of the
-    grower that share the model's rows and tree parameters (``G``, ``H`` and the margins are ``[P * K, N]``). What
-    couples them is the round epilogue: with ``p = softmax(margins)``, class k's next statistics are
-    ``g = p_k - [y == k]`` and ``h = max(2 p_k (1 - p_k), 1e-16)``. The base margin is ``base_score`` on every
-    class (it cancels in the softmax). Trees are stored round-major -- tree ``t`` belongs to class ``t % K`` -- and
-    early stopping (``merror``, the default, or ``mlogloss`` on the training rows, both minimised) keeps whole
-    rounds. (g, h) are zero outside a model's training rows, so their maxima over the training rows are the
-    maxima over all rows that the grower's fixed-point scales need.
-
-    On the GPU the epilogue is two launches (ops/csrc/hip/boost_multi_kernels.hip) and the trees grow on the
-    host-planned fused path: the device-resident level loop and the fused prologue take one maxima row and one
-    job per model, and are not used here."""
+    """Multiclass Newton boosting with :class:`_SoftmaxObjective` (``multi:softprob`` / ``multi:softmax``, see
+    :meth:`XGBoostClassifierLearner.fit_batch`); not registered. A model's K trees of a round are stored
+    round-major -- tree ``t`` belongs to class ``t % K`` -- and early stopping keeps whole rounds."""
 
     def __init__(self, n_classes: int, **params):
         super().__init__(**params)
@@ -1168,199 +1344,8 @@ class _SoftmaxXGBClassifier(XGBoostClassifierLearner):
         return self.K
 
     def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None):
-        K = self.K
-        P = len(jobs)
-        Q = P * K
-        rows = [_rows(j, N, dev).to(torch.int64).contiguous() for j in jobs]
-        n_rows = [max(1, int(r.numel())) for r in rows]
-        rounds = [int(j.params.get("num_round", 100)) for j in jobs]
-        esr = [int(j.params.get("num_early_stopping_rounds", 0)) for j in jobs]
-        metric = []
-        for j in jobs:
-            em = j.params.get("eval_metric", "aucpr")
-            em = "merror" if em == "aucpr" else em          # the classifier's default metric is the binary one
-            if em not in ("merror", "mlogloss"):
-                raise ValueError(f"eval_metric {em} not supported for a multiclass objective")
-            metric.append(em)
-        base = [float(j.params.get("base_score", 0.5)) for j in jobs]
-        Fm = to_device(np.repeat(np.asarray(base, np.float64), K), dev, np.float64)[:, None].repeat(1, N)
-        yl = y.to(torch.int64)
-        yf = y.to(torch.float32).contiguous()
-        cls = torch.arange(K, device=dev)[:, None]
-        forests, weights = [[] for _ in range(P)], [[] for _ in range(P)]
-        best = [-float("inf")] * P
-        best_round = [0] * P
-        stopped = [False] * P
-        fused = dev.type == "cuda" and all(float(j.params.get("subsample", 1.0)) >= 1.0 for j in jobs) and \
-            os.environ.get("TMOG_XGB_FUSED", "1") != "0"
-        Xg, n_bins_g, colperm, Xh, fp, csr, XgT = _xgb_growth_matrix(Xb, spec, dev, par)
-        wide = TE.wide_rows(int(Xg.shape[0]))
-        # shared [P K, N] statistics: a model's K rows are only touched by the part that boosts the model
-        G = torch.zeros(Q, N, dtype=torch.float32, device=dev)
-        H = torch.zeros(Q, N, dtype=torch.float32, device=dev)
-        # the softmax kernel's per-pseudo-job maxima of (|g|, h) are the next round's quantisation maxima
-        # (TMOG_XGB_AMAX=0: the grower scans [P K, N] every round instead)
-        tam = amax_cur = None
-        if fused and os.environ.get("TMOG_XGB_AMAX", "1") != "0":
-            tam = torch.zeros(64, Q, 2, dtype=torch.int32, device=dev)      # boost_multi_kernels.hip kAmaxCopies
-            amax_cur = torch.zeros(Q, 2, dtype=torch.float32, device=dev)
-        es_lag = max(1, int(os.environ.get("TMOG_ES_LAG", "2"))) if fused else 1
-
-        def pseudo(ps):
-            return [p * K + k for p in ps for k in range(K)]
-
-        def grad_torch(ps):
-            """Reference epilogue in torch fp64: the models' (g, h) from their margins, on their rows."""
-            for p in ps:
-                r = rows[p]
-                pr = torch.softmax(Fm[p * K:(p + 1) * K].index_select(1, r), 0)
-                g = pr - (yl[r][None, :] == cls).to(torch.float64)
-                h = (2.0 * pr * (1.0 - pr)).clamp_min(1e-16)
-                G[p * K:(p + 1) * K].index_copy_(1, r, g.to(torch.float32))
-                H[p * K:(p + 1) * K].index_copy_(1, r, h.to(torch.float32))
-
-        def metric_torch(p):
-            m = Fm[p * K:(p + 1) * K].index_select(1, rows[p])
-            lab = yl[rows[p]]
-            if metric[p] == "merror":
-                return (m.argmax(0) != lab).to(torch.float64).sum() / n_rows[p]
-            return -torch.log_softmax(m, 0).gather(0, lab.clamp(0, K - 1)[None, :]).sum() / n_rows[p]
-
-        def run(ps, slot_base=0, groups=None):
-            """Boosting rounds of the models ``ps`` (all K pseudo-jobs of a model run in the same part: the softmax
-            reads all K margins; the trees do not depend on which other models grow alongside)."""
-            root_cache: Dict[tuple, tuple] = {}
-            lists: Dict[tuple, tuple] = {}
-            pending: list = []
-
-            def grad_fused(act, err):
-                key = tuple(act)
-                if key not in lists:
-                    lists.clear()
-                    off = np.concatenate([[0], np.cumsum([int(rows[p].numel()) for p in act])]).astype(np.int64)
-                    lists[key] = (torch.cat([rows[p] for p in act]), TE._const_tensor(off, dev),
-                                  TE._const_tensor(np.asarray(act, np.int64), dev),
-                                  max(int(rows[p].numel()) for p in act),
-                                  TE._const_tensor(np.asarray(pseudo(act), np.int64), dev))
-                cat, off_t, mod_t, longest, qi = lists[key]
-                if tam is not None:
-                    tam.index_fill_(1, qi, 0)
-                self._softmax_grad(cat, off_t, mod_t, len(act), longest, K, N, P, Fm, yf, G, H, tam, err)
-                if tam is not None:
-                    amax_cur.index_copy_(0, qi, tam.index_select(1, qi).view(torch.float32).amax(0))
-
-            def resolve(it0, need0, vals_t):
-                for p, v in zip(need0, vals_t.tolist()):
-                    if stopped[p]:
-                        continue
-                    if v > best[p] + 1e-12:
-                        best[p], best_round[p] = v, it0
-                    elif it0 - best_round[p] >= esr[p]:
-                        stopped[p] = True
-
-            if fused:
-                first = [p for p in ps if rounds[p] > 0]
-                if first:
-                    grad_fused(first, None)
-            for it in range(max([rounds[p] for p in ps], default=0)):
-                cancel.check()
-                act = [p for p in ps if it < rounds[p] and not stopped[p]]
-                if not act:
-                    break
-                if not fused:
-                    grad_torch(act)
-                tjobs = []
-                for p in act:
-                    pr = jobs[p].params
-                    tp = TE.TreeParams(max_depth=int(pr.get("max_depth", 6)),
-                                       min_child_weight=float(pr.get("min_child_weight", 1.0)),
-                                       reg_lambda=float(pr.get("reg_lambda", 1.0)), gamma=float(pr.get("gamma", 0.0)),
-                                       eta=float(pr.get("eta", 0.3)), split_eps=1e-6)
-                    w = None
-                    ss = float(pr.get("subsample", 1.0))
-                    if ss < 1.0:        # one row sample per model and round, shared by its K trees
-                        gen = torch.Generator().manual_seed(int(pr.get("seed", 0)) + 17 * it + p)
-                        w = (torch.rand(rows[p].numel(), generator=gen) < ss).to(torch.int64).to(dev)
-                    tjobs += [TE.TreeJob(p * K + k, tp, rows[p], w) for k in range(K)]
-                qact = pseudo(act)
-                root = None
-                if all(j.weights is None for j in tjobs):
-                    key = tuple(act)
-                    if key not in root_cache:
-                        root_cache.clear()
-                        root_cache[key] = TE._root_rows(tjobs, dev, wide)
-                    packed, cnts = root_cache[key]
-                    root = (packed.clone(), cnts)
-                forest = TE.grow_forest(Xg, n_bins_g, tjobs, mode=TE.MODE_GH, kind=TE.KIND_NEWTON, t1=G, t2=H, B=mb,
-                                        missing_bin=spec.missing_bin, collect_leaves=True, csr=csr, root=root, fp=fp,
-                                        slot_base=slot_base, groups=groups, XbT=XgT, quant_amax=amax_cur,
-                                        quant_wmax=1.0 if amax_cur is not None else None, Xh=Xh)
-                if colperm is not None:
-                    internal = forest.nodes[:, 2] >= 0
-                    forest.nodes[internal, 0] = colperm[forest.nodes[internal, 0]]
-                need = [p for p in act if esr[p] > 0]
-                err = None
-                if fused:
-                    self._margin_add(Fm, forest, qact, N)
-                    if any(metric[p] == "merror" for p in need):
-                        err = torch.zeros(P, dtype=torch.int32, device=dev)
-                    grad_fused(act, err)
-                else:
-                    _add_tree_margins(Fm, forest, Xb, qact, [1.0] * len(qact), tjobs)
-                for k_, q in enumerate(qact):        # round-major: class k's tree of this round at index it * K + k
-                    forests[q // K].append(forest.tree(k_))
-                    weights[q // K].append(1.0)
-                # early stopping on the training metric, read back es_lag rounds late (the final trim drops
-                # the trees grown meanwhile); both metrics are minimised: the negated value is maximised
-                if need:
-                    vals = [err[p].to(torch.float64) / n_rows[p] if (err is not None and metric[p] == "merror")
-                            else metric_torch(p) for p in need]
-                    while len(pending) >= es_lag:
-                        resolve(*pending.pop(0))
-                    pending.append((it, need, -torch.stack(vals)))
-            while pending:
-                resolve(*pending.pop(0))
-
-        parts = int(os.environ.get("TMOG_XGB_PIPE", "4"))
-        if fused and par is None and P >= 2 and parts >= 2:
-            # pipelined parts cut between models, never inside one
-            parts = min(parts, P)
-            cuts = np.linspace(0, P, parts + 1).astype(int)
-            gpp = max(1, int(os.environ.get("TMOG_XGB_PIPE_GROUPS", "1")))
-            _run_parts(dev, [(list(range(int(cuts[k]), int(cuts[k + 1]))), k * gpp, gpp) for k in range(parts)], run)
-        else:
-            run(list(range(P)))
-        res = []
-        for p in range(P):
-            keep = K * (len(forests[p]) // K if not stopped[p] else best_round[p] + 1)
-            res.append({"forest": TE.Forest.concat(forests[p][:keep]).to_state(), "bins": spec.to_state(),
-                        "tree_weights": np.asarray(weights[p][:keep], np.float32), "n_classes": K,
-                        "max_bins": mb, "base_margin": base[p], "num_trees": keep,
-                        "objective": str(jobs[p].params.get("objective", "multi:softprob"))})
-        return res
-
-    @staticmethod
-    def _margin_add(Fm, forest, qact, N):
-        """Margins of the round's pseudo-jobs += their trees' leaf values, from the leaf assignment."""
-        from ..ops import _native as NV
-        la = forest.leaf_assign
-        dev = Fm.device
-        val = la.value[:, 0].contiguous() if la.value.dim() == 2 else la.value.contiguous()
-        tree_job = TE._const_tensor(np.asarray(qact, np.int64), dev)
-        tree_c = la.tree.contiguous()
-        NV.check(NV.hip().tmog_hip_boost_margin_add(
-            NV.ptr(la.rows), NV.ptr(la.gid), int(la.rows.numel()), NV.ptr(val), NV.ptr(tree_c), NV.ptr(tree_job),
-            int(N), NV.ptr(Fm), int(val.shape[0]), len(qact), int(Fm.shape[0]), int(getattr(la, "wide", False)),
-            NV.stream(dev)), "boost_margin_add")
-
-    @staticmethod
-    def _softmax_grad(cat, off, models, M, longest, K, N, P, Fm, yf, G, H, tam, err):
-        """(g, h) of the ``M`` listed models on their training rows from the softmax of their margins, the
-        per-pseudo-job maxima into ``tam`` and (with ``err``) the per-model argmax error counts."""
-        from ..ops import _native as NV
-        NV.check(NV.hip().tmog_hip_softmax_grad(
-            NV.ptr(cat), NV.ptr(off), NV.ptr(models), int(M), int(longest), int(K), int(N), int(P), NV.ptr(Fm),
-            NV.ptr(yf), NV.ptr(G), NV.ptr(H), NV.ptr(tam), NV.ptr(err), NV.stream(Fm.device)), "softmax_grad")
+        res = _newton_boost(functools.partial(_SoftmaxObjective, self.K), True, Xb, spec, y, jobs, N, dev, mb, par)
+        return [dict(r, objective=str(j.params.get("objective", "multi:softprob"))) for r, j in zip(res, jobs)]
 
 
 @register_learner
@@ -1370,13 +1355,7 @@ class XGBoostRegressorLearner(XGBoostClassifierLearner):
     classification = False
     defaults = dict(XGBoostClassifierLearner.defaults, objective="reg:squarederror", eval_metric="rmse",
                     maximize_evaluation_metrics=False)
-    objective_code = 1
-
-    def _grad(self, yy, Fm):
-        return Fm - yy, torch.ones_like(Fm)
-
-    def _base_margin(self, bs):
-        return float(bs)
+    _objective = _SquaredErrorObjective
 
     def _outputs(self, state, m):
         e = torch.zeros(m.shape[0], 0, dtype=torch.float64, device=m.device)
