@@ -848,6 +848,14 @@ constexpr int FPB = 16;      // default features per scan workgroup (TMOG_SPLIT_
 // finished (the fused split reduction's sc1 hand-off)
 static inline int cand_stride(int fbmax) { return (fbmax + 15) & ~15; }
 
+// TMOG_SCAN_GENERIC=1: kind 3 (Newton) also takes the generic instantiation of the narrow scans (run-time kind,
+// unpipelined loads) -- the reference of the Newton instantiation. Read at every launch: tests toggle it.
+static bool scan_newton(int kind, int S) {
+  if (kind != 3 || S != 2) return false;       // Newton statistics are (g, h); S is compile-time there
+  const char* e = std::getenv("TMOG_SCAN_GENERIC");
+  return !(e && e[0] == '1');
+}
+
 static int split_fpb() {
   static const int v = [] {
     const char* e = std::getenv("TMOG_SPLIT_FPB");
@@ -941,7 +949,10 @@ __device__ __forceinline__ void reduce_node(const ReduceArgs& ra, int j, int lan
 
 // Per-node split evaluation state of the narrow scans (split_scan_kernel, pair_scan_kernel): node totals
 // (fixed point and scaled), the node's parameters, and this thread's best candidate so far.
-template <int SM>
+// NEWTON: the gain kind is 3 at compile time (XGBoost's only kind) -- the instantiation holds no impurity code
+// (Gini, entropy's fp64 log2, variance), which the run-time kind inlines at every consider() site; the Newton
+// expressions and their order are those of the generic instantiation's kind == 3 branch.
+template <int SM, bool NEWTON = false>
 struct NodeScan {
   int64_t totq[SM];
   double tot[SM], q[SM];
@@ -954,7 +965,7 @@ struct NodeScan {
   __device__ __forceinline__ void init(const int64_t* totq_in, const double* qi, const float* P, int S_, int kind_,
                                        int missing_bin) {
     S = S_;
-    kind = kind_;
+    kind = NEWTON ? 3 : kind_;
     best = Best{-INFINITY, 0x7fffffff, 0, 0};
     min_inst = P[0];
     min_gain = P[1];
@@ -966,8 +977,12 @@ struct NodeScan {
       q[s] = qi[s];
       tot[s] = (double)totq[s] * q[s];
     }
-    pimp = impurity_reg<SM>(tot, S, kind, &tcount);
-    parent_gain = kind == 3 ? tot[0] * tot[0] / (tot[1] + lambda) : 0.0;
+    if constexpr (NEWTON) {
+      parent_gain = tot[0] * tot[0] / (tot[1] + lambda);
+    } else {
+      pimp = impurity_reg<SM>(tot, S, kind, &tcount);
+      parent_gain = kind == 3 ? tot[0] * tot[0] / (tot[1] + lambda) : 0.0;
+    }
   }
 
   // one candidate (left statistics lq, bin b, missing direction dl) with the CPU twin's arithmetic
@@ -979,11 +994,11 @@ struct NodeScan {
     }
     double gain;
     bool ok = true;
-    if (kind == 3) {
+    if (NEWTON || kind == 3) {
       // invalid by min_child_weight: skip the two fp64 divisions (whole waves skip at small nodes)
       if (left[1] < mcw || right[1] < mcw) return;
       gain = left[0] * left[0] / (left[1] + lambda) + right[0] * right[0] / (right[1] + lambda) - parent_gain;
-    } else {
+    } else if constexpr (!NEWTON) {
       double lc, rc;
       const double li = impurity_reg<SM>(left, S, kind, &lc);
       const double ri = impurity_reg<SM>(right, S, kind, &rc);
@@ -1039,7 +1054,36 @@ __device__ __forceinline__ void node_totals(const int64_t* h, int B, int S, int 
   TM_FOR_S(s) totq[s] = readlane64(wave_scan64(v[s]), 63);
 }
 
+// The row of feature f that a lane of the narrow scans reads: its own bin's (bin 0 past the B bins, so every
+// load is unconditional). The Newton instantiations issue these one feature ahead of the scan that uses them.
 template <int SM>
+__device__ __forceinline__ void load_row(const int64_t* __restrict__ h, int f, int B, int S, int lane, int64_t* v) {
+  const int64_t o = (int64_t)f * B * S + (lane < B ? lane : 0) * S;
+  TM_FOR_S(s) v[s] = h[o + s];
+}
+
+// End of a batch of independent wave-uniform loads: they are all issued above this point and their values
+// (scalar registers) are complete below it, whatever uses them first.
+template <class T>
+__device__ __forceinline__ void pin_scalar(T& v) {
+  asm volatile("" : "+s"(v));
+}
+template <class... T>
+__device__ __forceinline__ void batch_end(T&... v) {
+  __builtin_amdgcn_sched_barrier(0);
+  (pin_scalar(v), ...);
+}
+
+// node_totals from the lane's row of local feature 0 (load_row), already loaded
+template <int SM>
+__device__ __forceinline__ void row_totals(const int64_t* row, int B, int S, int lane, int64_t* totq) {
+  TM_FOR_S(s) totq[s] = readlane64(wave_scan64(lane < B ? row[s] : 0), 63);
+}
+
+// NEWTON: compile-time gain kind 3 (NodeScan) and a software-pipelined feature loop -- the rows of the wave's next
+// feature are in flight while it scans the current one. The generic instantiation keeps the run-time kind and the
+// load -> wait -> scan loop (TMOG_SCAN_GENERIC=1 selects it for kind 3 too: the reference of the Newton one).
+template <int SM, bool NEWTON>
 __global__ void __launch_bounds__(256) split_scan_kernel(
     const int64_t* __restrict__ hist, const int64_t* __restrict__ node_hist_off, const int32_t* __restrict__ node_nfeat,
     const int32_t* __restrict__ node_feat_off, const int32_t* __restrict__ feat_list,
@@ -1048,10 +1092,13 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
     Best* __restrict__ cand, int n_multi, int fpb, unsigned* __restrict__ done, ReduceArgs ra,
     const int* __restrict__ dm) {
   const int cstride = ra.cstride;
+  if constexpr (NEWTON) S = SM;      // the launcher takes this instantiation at S == SM only: no run-time S guards
   const int j = blockIdx.x / fbmax;
   const int fb = blockIdx.x - j * fbmax;
   if (dm != nullptr && j >= *dm) return;      // device-planned level: node count on the device
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  // NEWTON: the wave index as a scalar, so the feature index, its bin count and row offset are too
+  const int wave = NEWTON ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
   // params slot 4: the node was scanned with its subtraction partner by pair_scan_kernel (same cand slots, all
   // written by that earlier launch): with the fused reduction its block 0 reduces it, the others have nothing to do
   if (node_params[(int64_t)j * 8 + 4] > 0.5f) {
@@ -1065,18 +1112,37 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
   const int fb_multi = n_multi >= 0 ? (n_multi + fpb - 1) / fpb : fbmax;
   const bool one_blk = fb >= fb_multi;
   __shared__ Best s_best[4];
-  NodeScan<SM> ns;
+  NodeScan<SM, NEWTON> ns;
   ns.best = Best{-INFINITY, 0x7fffffff, 0, 0};
   // params slot 7 = "may split" (tree_grow.hpp): nodes built only as a subtraction partner are not scanned
   if (node_params[(int64_t)j * 8 + 7] > 0.5f &&
       (one_blk ? (n_multi + (fb - fb_multi) * 256 < nf) : (fb * fpb < f_lim))) {
     const int64_t* h = hist + node_hist_off[j];
     const int32_t* fl = feat_list + node_feat_off[j];
+    const int f_end = one_blk ? 0 : min(f_lim, (fb + 1) * fpb);
+    const int mbin = missing_bin >= 0 ? missing_bin : 0;
+    // NEWTON: the next feature's bin count, own-bin row and missing-bin row, issued a feature ahead -- the first
+    // feature's here, with the node totals' rows, the following one's before each scan
+    [[maybe_unused]] int64_t nv[SM], nm[SM];
+    [[maybe_unused]] int nb_next = 0;
+    [[maybe_unused]] auto issue = [&](int f) {
+      load_row<SM>(h, f, B, S, lane, nv);
+      const int64_t* hf = h + (int64_t)f * B * S;
+      TM_FOR_S(s) nm[s] = hf[mbin * S + s];
+      nb_next = feat_nbins[fl[f]];
+    };
     int64_t totq[SM];
-    node_totals<SM>(h, B, S, lane, totq);
+    if constexpr (NEWTON) {
+      int64_t r0[SM];
+      load_row<SM>(h, 0, B, S, lane, r0);
+      if (fb * fpb + wave < f_end) issue(fb * fpb + wave);
+      __builtin_amdgcn_sched_barrier(0);
+      row_totals<SM>(r0, B, S, lane, totq);
+    } else {
+      node_totals<SM>(h, B, S, lane, totq);
+    }
     ns.init(totq, qinv + (int64_t)(node_model ? node_model[j] : 0) * S, node_params + (int64_t)j * 8, S, kind,
             missing_bin);
-    const int f_end = one_blk ? 0 : min(f_lim, (fb + 1) * fpb);
     if (one_blk) {
       const int f = n_multi + (fb - fb_multi) * 256 + (int)threadIdx.x;
       if (f < nf && ns.allow_missing && feat_nbins[fl[f]] == 1) {
@@ -1086,31 +1152,52 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
         ns.consider(lq, f, 0, 0);
       }
     }
-    for (int f = fb * fpb + wave; f < f_end; f += 4) {
-      const int nb = feat_nbins[fl[f]];
-      const int64_t* hf = h + (int64_t)f * B * S;
-      if (nb == 1) {
-        // one present bin (one-hot / null indicator): the only candidate is present-left,
-        // missing-right -- no scan, one lane
-        if (ns.allow_missing && lane == 0) {
-          int64_t lq[SM];
-          TM_FOR_S(s) lq[s] = hf[s];
-          ns.consider(lq, f, 0, 0);
+    if constexpr (NEWTON) {
+      for (int f = fb * fpb + wave; f < f_end; f += 4) {
+        int64_t v[SM], miss[SM];
+        const int nb = nb_next;
+        TM_FOR_S(s) {
+          v[s] = nv[s];
+          miss[s] = nm[s];
         }
-        continue;
+        if (f + 4 < f_end) issue(f + 4);
+        __builtin_amdgcn_sched_barrier(0);      // the next feature's loads stay ahead of this one's scan
+        if (nb == 1) {       // one present bin: lane 0 holds bin 0 (see the generic loop)
+          if (ns.allow_missing && lane == 0) ns.consider(v, f, 0, 0);
+          continue;
+        }
+        TM_FOR_S(s) {
+          v[s] = lane < nb ? v[s] : 0;
+          miss[s] = ns.allow_missing ? miss[s] : 0;
+        }
+        ns.scan_feature(v, miss, nb, f, lane);
       }
-      int64_t v[SM], miss[SM];
-      const int bl = lane < nb ? lane : 0;
-      const int mbin = missing_bin >= 0 ? missing_bin : 0;
-      TM_FOR_S(s) {          // unconditional loads, selected afterwards (issued together)
-        v[s] = hf[bl * S + s];
-        miss[s] = hf[mbin * S + s];
+    } else {
+      for (int f = fb * fpb + wave; f < f_end; f += 4) {
+        const int nb = feat_nbins[fl[f]];
+        const int64_t* hf = h + (int64_t)f * B * S;
+        if (nb == 1) {
+          // one present bin (one-hot / null indicator): the only candidate is present-left,
+          // missing-right -- no scan, one lane
+          if (ns.allow_missing && lane == 0) {
+            int64_t lq[SM];
+            TM_FOR_S(s) lq[s] = hf[s];
+            ns.consider(lq, f, 0, 0);
+          }
+          continue;
+        }
+        int64_t v[SM], miss[SM];
+        const int bl = lane < nb ? lane : 0;
+        TM_FOR_S(s) {          // unconditional loads, selected afterwards (issued together)
+          v[s] = hf[bl * S + s];
+          miss[s] = hf[mbin * S + s];
+        }
+        TM_FOR_S(s) {
+          v[s] = lane < nb ? v[s] : 0;
+          miss[s] = ns.allow_missing ? miss[s] : 0;
+        }
+        ns.scan_feature(v, miss, nb, f, lane);
       }
-      TM_FOR_S(s) {
-        v[s] = lane < nb ? v[s] : 0;
-        miss[s] = ns.allow_missing ? miss[s] : 0;
-      }
-      ns.scan_feature(v, miss, nb, f, lane);
     }
   }
   ns.wave_best();
@@ -1163,7 +1250,17 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
 // again by a separate scan. Node totals: small from its feature 0, big = parent's - small's. Writes
 // cand[j_small][fb] and cand[j_big][fb]; the two nodes carry params slot 4 = 1 so split_scan_kernel skips
 // them. Words outside the live set (one-present-bin columns above bin 0) are left alone, as before.
-template <int SM>
+// Load schedule. The kernel is bound by exposed load latency, not by VALU issue or bandwidth (profiles/README.md):
+// a wave runs a chain of dependent loads (pair -> node offsets -> rows) and then up to four features of ~400
+// VALU instructions each. The generic instantiation (run-time kind) waits for each feature's rows right before
+// scanning them. The NEWTON instantiation (kind 3 at compile time, no impurity code: fewer registers, more
+// resident waves) keeps one feature in flight: the first feature's rows and bin count are issued with the node
+// totals' rows as soon as the node offsets are known, and each feature's successor is issued before the current
+// one is scanned (the sched_barrier keeps the compiler from sinking those loads). The current rows are complete
+// before the successor's loads go out, the big child's stores follow them in program order, and the next wait
+// on the vector memory counter stands after the scan: no store drains the prefetch.
+// The wave index is a scalar there, so feature index, bin count and row base live in SGPRs.
+template <int SM, bool NEWTON>
 __global__ void __launch_bounds__(256) pair_scan_kernel(
     int64_t* __restrict__ hist, const int64_t* __restrict__ parent, const int64_t* __restrict__ parent_off,
     const int32_t* __restrict__ small_j, const int32_t* __restrict__ big_j, int n_pairs,
@@ -1172,34 +1269,95 @@ __global__ void __launch_bounds__(256) pair_scan_kernel(
     const int32_t* __restrict__ feat_nbins, int B, int S, int kind, const float* __restrict__ node_params,
     int missing_bin, const int32_t* __restrict__ node_model, const double* __restrict__ qinv, int fbmax,
     Best* __restrict__ cand, int n_multi, int fpb, int cstride, const int* __restrict__ dnp) {
+  if constexpr (NEWTON) S = SM;      // the launcher takes this instantiation at S == SM only: no run-time S guards
   const int q = blockIdx.x / fbmax;
   const int fb = blockIdx.x - q * fbmax;
   if (dnp != nullptr) n_pairs = *dnp;          // device-planned level: pair count on the device
   if (q >= n_pairs) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int js = small_j[q], jb = big_j[q];
-  const int nf = node_nfeat[js];           // no per-node feature subsets on this path: same list for both
+  const int lane = threadIdx.x & 63;
+  const int wave = NEWTON ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
+  // NEWTON: the dependent loads of the prologue go out in three batches (batch_end(): the compiler otherwise
+  // issues them one by one, each waited for before the next): the pair; the two nodes' offsets and "may split"
+  // flags; the node totals' rows with the first feature's. The nodes' models, which only the scales need, are
+  // read behind the third.
+  int js = small_j[q], jb = big_j[q];
+  int64_t poff = parent_off[q];
+  if constexpr (NEWTON) batch_end(js, jb, poff);
+  int nf = node_nfeat[js];                 // no per-node feature subsets on this path: same list for both
+  int64_t hs_off = node_hist_off[js], hb_off = node_hist_off[jb];
+  int fl_off = node_feat_off[js];
+  float may_s = node_params[(int64_t)js * 8 + 7], may_b = node_params[(int64_t)jb * 8 + 7];
+  if constexpr (NEWTON) batch_end(nf, hs_off, hb_off, fl_off, may_s, may_b);
+  const int64_t* P = parent + poff;
+  const int64_t* Hs = hist + hs_off;
+  int64_t* Hb = hist + hb_off;
+  const int32_t* fl = feat_list + fl_off;
+  const bool scan_s = may_s > 0.5f, scan_b = may_b > 0.5f;
   const int f_lim = n_multi >= 0 ? min(n_multi, nf) : nf;
   const int fb_multi = n_multi >= 0 ? (n_multi + fpb - 1) / fpb : fbmax;
   const bool one_blk = fb >= fb_multi;
-  const int64_t* P = parent + parent_off[q];
-  const int64_t* Hs = hist + node_hist_off[js];
-  int64_t* Hb = hist + node_hist_off[jb];
-  const int32_t* fl = feat_list + node_feat_off[js];
-  const bool scan_s = node_params[(int64_t)js * 8 + 7] > 0.5f;
-  const bool scan_b = node_params[(int64_t)jb * 8 + 7] > 0.5f;
+  const int f_end = one_blk ? 0 : min(f_lim, (fb + 1) * fpb);
+  // NEWTON: the next feature's bin count and this lane's rows of the built child and the parent, in flight
+  [[maybe_unused]] int64_t na[SM], np_[SM];
+  [[maybe_unused]] int nb_next = 0;
+  [[maybe_unused]] auto issue = [&](int f) {
+    load_row<SM>(Hs, f, B, S, lane, na);
+    load_row<SM>(P, f, B, S, lane, np_);
+    nb_next = feat_nbins[fl[f]];
+  };
   __shared__ Best s_best[2][4];
-  NodeScan<SM> ns, nb_;
+  NodeScan<SM, NEWTON> ns, nb_;
   {
     int64_t ts[SM], tp[SM], tb[SM];
-    node_totals<SM>(Hs, B, S, lane, ts);
-    node_totals<SM>(P, B, S, lane, tp);
+    if constexpr (NEWTON) {
+      int64_t rs[SM], rp[SM];
+      load_row<SM>(Hs, 0, B, S, lane, rs);
+      load_row<SM>(P, 0, B, S, lane, rp);
+      if (fb * fpb + wave < f_end) issue(fb * fpb + wave);
+      __builtin_amdgcn_sched_barrier(0);
+      row_totals<SM>(rs, B, S, lane, ts);
+      row_totals<SM>(rp, B, S, lane, tp);
+    } else {
+      node_totals<SM>(Hs, B, S, lane, ts);
+      node_totals<SM>(P, B, S, lane, tp);
+    }
     TM_FOR_S(s) tb[s] = tp[s] - ts[s];
-    ns.init(ts, qinv + (int64_t)(node_model ? node_model[js] : 0) * S, node_params + (int64_t)js * 8, S, kind,
-            missing_bin);
-    nb_.init(tb, qinv + (int64_t)(node_model ? node_model[jb] : 0) * S, node_params + (int64_t)jb * 8, S, kind,
-             missing_bin);
+    const int model_s = node_model ? node_model[js] : 0, model_b = node_model ? node_model[jb] : 0;
+    ns.init(ts, qinv + (int64_t)model_s * S, node_params + (int64_t)js * 8, S, kind, missing_bin);
+    nb_.init(tb, qinv + (int64_t)model_b * S, node_params + (int64_t)jb * 8, S, kind, missing_bin);
   }
+  // feature f from this lane's rows pa (built child) and pp (parent): the big child's row out, both scans
+  auto scan_pair = [&](int f, int nbins, const int64_t* pa, const int64_t* pp) {
+    const int64_t o = (int64_t)f * B * S;
+    int64_t vs[SM], vb[SM], ms[SM], mb[SM];
+    TM_FOR_S(s) {
+      const int64_t a = lane < B ? pa[s] : 0;
+      const int64_t c = lane < B ? pp[s] - pa[s] : 0;
+      if (lane < B) Hb[o + lane * S + s] = c;
+      // missing bin statistics from the lane holding it
+      ms[s] = missing_bin >= 0 ? readlane64(a, missing_bin) : 0;   // kernel argument: wave-uniform lane
+      mb[s] = missing_bin >= 0 ? readlane64(c, missing_bin) : 0;
+      vs[s] = lane < nbins ? a : 0;
+      vb[s] = lane < nbins ? c : 0;
+    }
+    if (nbins == 1) {
+      if (lane == 0) {
+        if (scan_s && ns.allow_missing) ns.consider(vs, f, 0, 0);
+        if (scan_b && nb_.allow_missing) nb_.consider(vb, f, 0, 0);
+      }
+      return;
+    }
+    if (scan_s) {
+      if (!ns.allow_missing)
+        TM_FOR_S(s) ms[s] = 0;
+      ns.scan_feature(vs, ms, nbins, f, lane);
+    }
+    if (scan_b) {
+      if (!nb_.allow_missing)
+        TM_FOR_S(s) mb[s] = 0;
+      nb_.scan_feature(vb, mb, nbins, f, lane);
+    }
+  };
   if (one_blk) {
     const int f = n_multi + (fb - fb_multi) * 256 + (int)threadIdx.x;
     if (f < nf) {
@@ -1215,44 +1373,25 @@ __global__ void __launch_bounds__(256) pair_scan_kernel(
         if (scan_b && nb_.allow_missing) nb_.consider(lb, f, 0, 0);
       }
     }
+  } else if constexpr (NEWTON) {
+    for (int f = fb * fpb + wave; f < f_end; f += 4) {
+      int64_t pa[SM], pp[SM];
+      const int nbins = nb_next;
+      TM_FOR_S(s) {
+        pa[s] = na[s];
+        pp[s] = np_[s];
+      }
+      if (f + 4 < f_end) issue(f + 4);
+      __builtin_amdgcn_sched_barrier(0);      // the next feature's loads stay ahead of this one's stores and scan
+      scan_pair(f, nbins, pa, pp);
+    }
   } else {
-    const int f_end = min(f_lim, (fb + 1) * fpb);
     for (int f = fb * fpb + wave; f < f_end; f += 4) {
       const int nbins = feat_nbins[fl[f]];
-      const int64_t o = (int64_t)f * B * S;
-      int64_t vs[SM], vb[SM], ms[SM], mb[SM], pa[SM], pp[SM];
-      const int bl = lane < B ? lane : 0;           // every load unconditional (issued together)
-      TM_FOR_S(s) {
-        pa[s] = Hs[o + bl * S + s];
-        pp[s] = P[o + bl * S + s];
-      }
-      TM_FOR_S(s) {
-        const int64_t a = lane < B ? pa[s] : 0;
-        const int64_t c = lane < B ? pp[s] - pa[s] : 0;
-        if (lane < B) Hb[o + lane * S + s] = c;
-        // missing bin statistics from the lane holding it
-        ms[s] = missing_bin >= 0 ? readlane64(a, missing_bin) : 0;   // kernel argument: wave-uniform lane
-        mb[s] = missing_bin >= 0 ? readlane64(c, missing_bin) : 0;
-        vs[s] = lane < nbins ? a : 0;
-        vb[s] = lane < nbins ? c : 0;
-      }
-      if (nbins == 1) {
-        if (lane == 0) {
-          if (scan_s && ns.allow_missing) ns.consider(vs, f, 0, 0);
-          if (scan_b && nb_.allow_missing) nb_.consider(vb, f, 0, 0);
-        }
-        continue;
-      }
-      if (scan_s) {
-        if (!ns.allow_missing)
-          TM_FOR_S(s) ms[s] = 0;
-        ns.scan_feature(vs, ms, nbins, f, lane);
-      }
-      if (scan_b) {
-        if (!nb_.allow_missing)
-          TM_FOR_S(s) mb[s] = 0;
-        nb_.scan_feature(vb, mb, nbins, f, lane);
-      }
+      int64_t pa[SM], pp[SM];
+      load_row<SM>(Hs, f, B, S, lane, pa);           // every load unconditional (issued together)
+      load_row<SM>(P, f, B, S, lane, pp);
+      scan_pair(f, nbins, pa, pp);
     }
   }
   ns.wave_best();
@@ -1964,14 +2103,15 @@ int tmog_hip_split_find(const int64_t* hist, int n_nodes, const int64_t* node_hi
   fbmax = n_multi >= 0 ? (n_multi + fpb - 1) / fpb + (max_nfeat - n_multi + 255) / 256
                        : (max_nfeat + fpb - 1) / fpb;
   ra = make_ra(fbmax);
-#define TM_SPLIT(SMV)                                                                                          \
-  hipLaunchKernelGGL(split_scan_kernel<SMV>, dim3(n_nodes * fbmax), dim3(256), 0, stream, hist, node_hist_off,  \
+#define TM_SPLIT(...)                                                                                          \
+  hipLaunchKernelGGL((split_scan_kernel<__VA_ARGS__>), dim3(n_nodes * fbmax), dim3(256), 0, stream, hist, node_hist_off,  \
                      node_nfeat, node_feat_off, feat_list, feat_nbins, B, S, kind, node_params, missing_bin,    \
                      node_model, qinv, fbmax, cand, n_multi, fpb, done, ra, dm)
-  if (S <= 2) TM_SPLIT(2);
-  else if (S == 3) TM_SPLIT(3);
-  else if (S <= 4) TM_SPLIT(4);
-  else TM_SPLIT(TM_MAX_S);
+  if (scan_newton(kind, S)) TM_SPLIT(2, true);
+  else if (S <= 2) TM_SPLIT(2, false);
+  else if (S == 3) TM_SPLIT(3, false);
+  else if (S <= 4) TM_SPLIT(4, false);
+  else TM_SPLIT(TM_MAX_S, false);
 #undef TM_SPLIT
   }
   if (wide) ra = make_ra(fbmax);
@@ -1994,15 +2134,16 @@ int tmog_hip_pair_scan(int64_t* hist, const int64_t* parent, const int64_t* pare
   const int fpb = split_fpb();
   const int fbmax = n_multi >= 0 ? (n_multi + fpb - 1) / fpb + (max_nfeat - n_multi + 255) / 256
                                  : (max_nfeat + fpb - 1) / fpb;
-#define TM_PAIR(SMV)                                                                                           \
-  hipLaunchKernelGGL(pair_scan_kernel<SMV>, dim3(n_pairs * fbmax), dim3(256), 0, stream, hist, parent, parent_off, \
+#define TM_PAIR(...)                                                                                           \
+  hipLaunchKernelGGL((pair_scan_kernel<__VA_ARGS__>), dim3(n_pairs * fbmax), dim3(256), 0, stream, hist, parent, parent_off, \
                      small_j, big_j, n_pairs, node_hist_off, node_nfeat, node_feat_off, feat_list, feat_nbins, B, S, \
                      kind, node_params, missing_bin, node_model, qinv, fbmax, (Best*)cand_ws, n_multi, fpb,    \
                      cand_stride(fbmax), dnp)
-  if (S <= 2) TM_PAIR(2);
-  else if (S == 3) TM_PAIR(3);
-  else if (S <= 4) TM_PAIR(4);
-  else TM_PAIR(TM_MAX_S);
+  if (scan_newton(kind, S)) TM_PAIR(2, true);
+  else if (S <= 2) TM_PAIR(2, false);
+  else if (S == 3) TM_PAIR(3, false);
+  else if (S <= 4) TM_PAIR(4, false);
+  else TM_PAIR(TM_MAX_S, false);
 #undef TM_PAIR
   return (int)hipGetLastError();
 }
