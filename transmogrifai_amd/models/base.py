@@ -135,6 +135,11 @@ class Learner:
     def feature_contributions(self, state, d: int) -> Optional[np.ndarray]:
         return None
 
+    def shap_values(self, state, X: torch.Tensor, rows=None, context=None):
+        """Exact additive per-record attributions of the model's score (tree learners: TreeSHAP)."""
+        raise NotImplementedError(f"{self.name} has no exact SHAP attributions; RecordInsightsLOCO explains "
+                                  "any model")
+
     def state_to_json(self, state: dict) -> dict:
         from ..utils.serde import encode
         return encode(state)

@@ -1171,3 +1171,164 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
             N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w),
             N.ptr(nodes), N.ptr(dl), forest.missing_bin, N.ptr(lv), K, N.ptr(out)), "forest_predict_cpu")
     return [out[int(mro[m]):int(mro[m + 1])] for m in range(len(model_rows))]
+
+
+# ------------------------------------------------------------------------------------------ TreeSHAP
+@dataclass
+class ForestPaths:
+    """One merged path per leaf (:func:`forest_paths`), ordered by length bin (m <= 16, <= 32, <= 64, longer),
+    then by tree. Element arrays are indexed ``p_off[p] .. p_off[p + 1]``."""
+    used: np.ndarray                # int32 [U]   distinct split features, sorted
+    p_off: np.ndarray               # int64 [P+1] element offsets
+    p_out: np.ndarray               # int32 [P]   first output column of the path
+    p_val: np.ndarray               # float64 [P, KV]  leaf value x tree weight
+    bias: np.ndarray                # float64 [n_out]  sum over paths of value x product of zero fractions
+    e_feat: np.ndarray              # int32 [E]   compact used-feature index
+    e_rng: np.ndarray               # int32 [E]   lo | hi << 12 | (missing bin satisfies) << 24
+    e_z: np.ndarray                 # float64 [E] zero fraction
+    bin_off: np.ndarray             # int64 [4]   path index bounds of the three kernel length bins
+    n_out: int                      # output columns the paths need
+    S: float                        # sum_t |w_t| max_node |value_t|: the attribution's magnitude bound
+    missing_bin: int = -1
+    _dev: dict = field(default_factory=dict, repr=False)
+
+    @property
+    def scale(self) -> float:
+        """The power of two with ``S * scale < 2^62`` (fixed-point accumulation of the HIP kernel)."""
+        if not (self.S > 0 and math.isfinite(self.S)):
+            return 1.0
+        return 2.0 ** max(-1000, min(1000, 62 - math.frexp(self.S)[1]))
+
+    def on(self, dev):
+        """The arrays the kernel reads, resident on ``dev`` (shipped once)."""
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (
+                self.used, self.p_off, self.p_out, self.p_val, self.e_feat, self.e_rng, self.e_z))
+        return self._dev[key]
+
+
+def forest_paths(forest: Forest, tree_weight: Optional[np.ndarray] = None,
+                 tree_out: Optional[np.ndarray] = None) -> ForestPaths:
+    """Unroll a forest into the leaf paths exact TreeSHAP works on. A feature that repeats on a path is merged
+    into one element: a row satisfies it iff it satisfies every merged node, i.e. its bin lies in the
+    intersection ``[lo, hi]`` of the nodes' ranges, or it is the missing bin and every merged node sends
+    missing rows along the path; the element's zero fraction is the product of the merged nodes' cover
+    ratios ``cover[child] / cover[node]`` (0 where ``cover[node] == 0``). A path carries its leaf's value
+    vector times the tree weight and the output column ``tree_out[t]`` (default 0) its first value goes to."""
+    T = forest.n_trees
+    KV = forest.K
+    tw = np.ones(T, np.float64) if tree_weight is None else np.asarray(tree_weight, np.float64)
+    tout = np.zeros(T, np.int32) if tree_out is None else np.asarray(tree_out, np.int32)
+    nd = forest.nodes
+    internal = nd[:, 2] >= 0
+    used = np.unique(nd[internal, 0]).astype(np.int32)
+    cover = forest.cover.astype(np.float64)
+    value = forest.value.astype(np.float64)
+    dl = forest.default_left
+    paths = []                       # (m, tree, feats, los, his, miss, zs, leaf)
+    S = 0.0
+    for t in range(T):
+        a, b = int(forest.tree_off[t]), int(forest.tree_off[t + 1])
+        if b <= a:
+            continue
+        S += abs(tw[t]) * float(np.abs(value[a:b]).max()) if value[a:b].size else 0.0
+        stack = [(a, ())]            # (node, elements: tuple of (feat, lo, hi, miss_ok, z) in order of first use)
+        while stack:
+            k, els = stack.pop()
+            f, sb, lc, rc = (int(v) for v in nd[k])
+            if lc < 0:
+                paths.append((len(els), t, els, k))
+                continue
+            ck = cover[k]
+            for child, left in ((rc, False), (lc, True)):
+                ratio = cover[child] / ck if ck != 0 else 0.0
+                lo, hi = (0, sb) if left else (sb + 1, 4095)
+                ok = bool(dl[k]) == left
+                for i, (ef, elo, ehi, eok, ez) in enumerate(els):
+                    if ef == f:
+                        ne = els[:i] + ((f, max(elo, lo), min(ehi, hi), eok and ok, ez * ratio),) + els[i + 1:]
+                        break
+                else:
+                    ne = els + ((f, lo, hi, ok, ratio),)
+                stack.append((child, ne))
+    lens = np.asarray([p[0] for p in paths], np.int64)
+    bins = np.searchsorted(np.asarray([16, 32, 64]), lens, side="left")
+    order = np.argsort(bins, kind="stable")                    # within a bin: tree order, as generated
+    P = len(paths)
+    p_off = np.zeros(P + 1, np.int64)
+    p_off[1:] = np.cumsum(lens[order])
+    E = int(p_off[-1])
+    p_out = np.zeros(P, np.int32)
+    p_val = np.zeros((P, KV), np.float64)
+    p_zprod = np.ones(P, np.float64)
+    e_feat = np.zeros(E, np.int32)
+    e_rng = np.zeros(E, np.int32)
+    e_z = np.zeros(E, np.float64)
+    for i, j in enumerate(order):
+        m, t, els, leaf = paths[j]
+        p_out[i] = tout[t]
+        p_val[i] = value[leaf] * tw[t]
+        o = int(p_off[i])
+        for e, (f, lo, hi, ok, z) in enumerate(els):
+            if lo > hi:
+                lo, hi = 1, 0                                  # contradictory repeats: no bin satisfies
+            e_feat[o + e] = f
+            e_rng[o + e] = lo | (hi << 12) | (int(ok) << 24)
+            e_z[o + e] = z
+            p_zprod[i] *= z
+    e_feat = np.searchsorted(used, e_feat).astype(np.int32)
+    sb = bins[order]
+    bin_off = np.asarray([0, np.sum(sb <= 0), np.sum(sb <= 1), np.sum(sb <= 2)], np.int64)
+    n_out = (int(tout.max()) if T else 0) + KV
+    bias = np.zeros(n_out, np.float64)
+    for c in range(KV):
+        np.add.at(bias, p_out + c, p_val[:, c] * p_zprod)
+    return ForestPaths(used, p_off, p_out, p_val, bias, e_feat, e_rng, e_z, bin_off, n_out, float(S),
+                       int(forest.missing_bin))
+
+
+def forest_shap(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                tree_weight: Optional[np.ndarray] = None, tree_out: Optional[np.ndarray] = None,
+                n_out: Optional[int] = None, paths: Optional[ForestPaths] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """Exact path-dependent TreeSHAP of the forest's ``tree_weight``-weighted leaf-value sum on rows ``rows``
+    (None = all) of the binned matrix: ``(phi float64 [n, U + 1, C], used_features int64 [U])``. Slot ``u < U``
+    is the attribution of column ``used_features[u]``, slot ``U`` the bias; tree ``t``'s ``K`` leaf values go to
+    columns ``tree_out[t] .. tree_out[t] + K - 1`` of ``C = n_out`` (default: as many as the trees need), and
+    ``phi.sum(1)`` equals the forest's prediction. Device matrices run ``tmog_hip_forest_shap``; paths longer
+    than 64 elements or a tile beyond the LDS limit, and host matrices, run the host twin. ``paths``: the
+    prepared :func:`forest_paths` of the same forest / weights / columns (callers cache them)."""
+    fp = paths if paths is not None else forest_paths(forest, tree_weight, tree_out)
+    C = int(n_out) if n_out is not None else fp.n_out
+    if C < fp.n_out:
+        raise ValueError(f"n_out = {C} but the trees write {fp.n_out} columns")
+    dev = Xb.device
+    Xb = Xb.contiguous()
+    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
+    if fp.used.size and int(fp.used[-1]) >= F:
+        raise ValueError(f"the forest splits on column {int(fp.used[-1])}, the matrix has {F}")
+    U, P, KV = int(fp.used.size), int(fp.p_out.size), int(fp.p_val.shape[1])
+    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
+    n = Nrows if rows is None else int(row_list.numel())
+    used64 = fp.used.astype(np.int64)
+    out = torch.empty(n, U + 1, C, dtype=torch.float64, device=dev)
+    bo = fp.bin_off
+    bias = np.zeros(C, np.float64)
+    bias[:fp.n_out] = fp.bias
+    if dev.type == "cuda":
+        d = fp.on(dev)
+        bias_d = torch.from_numpy(bias).to(dev)
+        rc = N.hip().tmog_hip_forest_shap(
+            N.ptr(Xb), F, n, N.ptr(row_list), U, N.ptr(d[0]), P, N.ptr(d[1]), N.ptr(d[2]), N.ptr(d[3]), KV,
+            N.ptr(bias_d), N.ptr(d[4]), N.ptr(d[5]), N.ptr(d[6]), bo.ctypes.data, fp.missing_bin, C, fp.scale,
+            N.ptr(out), N.stream(dev))
+        if rc in (-2, -3):           # a path longer than 64 elements / one row's tile beyond the LDS limit
+            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
+            return forest_shap(forest, sub.cpu(), None, n_out=C, paths=fp)[0].to(dev), used64
+        N.check(rc, "forest_shap")
+        return out, used64
+    N.check(N.host().tmog_forest_shap_cpu(
+        N.ptr(Xb), F, n, N.ptr(row_list), U, fp.used.ctypes.data, P, fp.p_off.ctypes.data, fp.p_out.ctypes.data,
+        fp.p_val.ctypes.data, KV, bias.ctypes.data, fp.e_feat.ctypes.data, fp.e_rng.ctypes.data,
+        fp.e_z.ctypes.data, bo.ctypes.data, fp.missing_bin, C, fp.scale, N.ptr(out)), "forest_shap_cpu")
+    return out, used64

@@ -345,6 +345,18 @@ class _ForestLearner(Learner):
     def predict(self, state, X, context=None):
         return self._outputs(state, self.raw_sum(state, X, None, context))
 
+    def shap_values(self, state, X, rows=None, context=None):
+        """Exact TreeSHAP of the additive score: ``(phi float64 [n, U + 1, C], used_features int64 [U])`` with
+        ``phi.sum(1)`` the raw class-vote sum of :meth:`raw_sum` (``C = K`` columns), for a regressor the
+        prediction (a forest's sum divided by its tree count). Slot ``U`` is the bias."""
+        forest, Xb = self._binned(state, X, context)
+        if "_shap_paths" not in state:
+            w = None
+            if not self.classification and self.is_forest:
+                w = np.full(forest.n_trees, 1.0 / max(1, int(state.get("num_trees", 1))))
+            state["_shap_paths"] = TE.forest_paths(forest, w)
+        return TE.forest_shap(forest, Xb, rows, paths=state["_shap_paths"])
+
     def predict_batch(self, states, X, rows, context=None):
         if not states:
             return []
@@ -585,6 +597,23 @@ class _BoostLearner(Learner):
 
     def predict(self, state, X, context=None):
         return self._outputs(state, self.margin(state, X, None, context))
+
+    def shap_values(self, state, X, rows=None, context=None):
+        """Exact TreeSHAP of the margin: ``(phi float64 [n, U + 1, C], used_features int64 [U])``, slot ``U``
+        the bias (``base_margin`` included). A regressor has one column, a binary classifier the two columns
+        ``(-phi, +phi)`` of its raw prediction ``(-m, m)``, a multiclass model one per class (tree ``t``
+        belongs to class ``t % K``)."""
+        forest, Xb = self._binned_for(state, X, context)
+        multi = state.get("objective") in MULTI_OBJECTIVES
+        K = int(state["n_classes"]) if multi else 1
+        if "_shap_paths" not in state:
+            tw = np.asarray(state["tree_weights"], np.float32).astype(np.float64)
+            state["_shap_paths"] = TE.forest_paths(forest, tw, np.arange(forest.n_trees) % K if multi else None)
+        phi, used = TE.forest_shap(forest, Xb, rows, n_out=K, paths=state["_shap_paths"])
+        phi[:, -1, :] += float(state.get("base_margin", 0.0))
+        if self.classification and not multi:
+            phi = torch.cat([-phi, phi], 2)
+        return phi, used
 
     def predict_batch(self, states, X, rows, context=None):
         return [self._outputs(s, self.margin(s, X, r, context)) for s, r in zip(states, rows)]

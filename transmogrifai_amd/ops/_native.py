@@ -34,6 +34,7 @@ _HOST_SIGS = {
                             I32],
     "tmog_partition_cpu": [P, I32, P, P, I32, P, P, P, P, P, I32, P, P, I32],
     "tmog_forest_predict_cpu": [P, I32, I32, P, P, P, P, P, P, P, I32, P, I32, P],
+    "tmog_forest_shap_cpu": [P, I32, I64, P, I32, P, I64, P, P, P, I32, P, P, P, P, P, I32, I32, C.c_double, P],
     "tmog_find_splits_cpu": [P, I64, I32, I32, P, P],
     "tmog_murmur3_batch": [P, P, I64, I32, P],
     "tmog_hash_index_batch": [P, P, I64, I32, I32, P],
@@ -105,6 +106,7 @@ _HIP_SIGS = {
     "tmog_hip_lr_epilogue_grad": [P, I64, I32, P, P, P, I32, I32, I32, P, I32, P, I32, P, P, P, I32, P],
     "tmog_hip_forest_predict": [P, I32, I32, P, P, I64, P, P, P, P, P, I32, P, I32, P, P],
     "tmog_hip_forest_predict_multi": [P, I32, I32, P, P, I64, P, P, P, P, P, I32, P, I32, P, P, P, P, P, P],
+    "tmog_hip_forest_shap": [P, I32, I64, P, I32, P, I64, P, P, P, I32, P, P, P, P, P, I32, I32, C.c_double, P, P],
     "tmog_hip_col_stats": [P, P, I64, I32, I64, P, P],
     "tmog_hip_vectorize_numeric": [P, P, P, I64, I32, P, P, P, P, I64, I32, P],
     "tmog_hip_onehot_pivot": [P, P, P, P, I32, I64, P, I64, P],

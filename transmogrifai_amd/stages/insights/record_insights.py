@@ -11,6 +11,9 @@ column) perturbation becomes one row of a perturbed batch scored by the model's 
 (for linear models the batch is never materialized: the perturbed margin is ``m_i - w_j x_ij``, an
 elementwise [rows, d] tensor op); top-K selection per record is ``torch.topk`` over the
 [rows, candidates] score-change matrix. Only the final ``TextMap`` strings are built on the host.
+
+Beyond the reference: ``RecordInsightsSHAP`` explains tree models with exact path-dependent TreeSHAP
+(``tree_engine.forest_shap``, HIP kernel ``ops/csrc/hip/shap_kernels.hip``) instead of perturbing columns.
 """
 from __future__ import annotations
 
@@ -295,6 +298,133 @@ class RecordInsightsLOCO(UnaryTransformer):
         from ...workflow.io import _build_stage
         self.model = _build_stage(a["model"]) if a.get("model") else None
         self.histories = a.get("histories")
+
+
+# ---------------------------------------------------------------------------------------------- SHAP
+@register_stage
+class RecordInsightsSHAP(RecordInsightsLOCO):
+    """Unary (OPVector -> TextMap) transformer wrapping a fitted tree model stage: exact path-dependent
+    TreeSHAP attributions of the model's additive score (the raw class-vote sums of a forest, the margin
+    of a boosted model; beyond the reference, which only has LOCO). The insights of a record plus the bias
+    add up to its raw prediction. Candidates come from the columns the trees split on; a text / date
+    column group (the grouping of ``RecordInsightsLOCO``) is one candidate worth the sum of its members --
+    SHAP is additive, so there is no aggregation strategy -- reported under its first active column (its
+    first split column when the record has none). Top-K selection is LOCO's, by the same score column."""
+    operation_name = "recordInsightsSHAP"
+    _defaults = {"top_k": 20, "top_k_strategy": "abs"}
+
+    def _shap(self, X: torch.Tensor, context=None):
+        learner, state = self._learner_state()
+        try:
+            return learner.shap_values(state, X, None, context)
+        except NotImplementedError as e:
+            raise ValueError(f"RecordInsightsSHAP needs a tree model: {e}") from e
+
+    def _shap_plan(self, hist: List[dict], used: np.ndarray, device):
+        """Candidates over the used columns: plain used columns first (in column order), then one per column
+        group with a used member. Returns (candidate of used slot [U], plain column per candidate (-1 for
+        groups) [m], per group (all its columns, its first used column))."""
+        member = {}
+        for g, cols in enumerate(self._groups(hist).values()):
+            for c in cols:
+                member[c] = (g, cols)
+        plain = [int(c) for c in used if int(c) not in member]
+        gids: Dict[int, int] = {}
+        gcols = []
+        cand = np.empty(len(used), np.int64)
+        k = 0
+        for u, c in enumerate(int(c) for c in used):
+            if c not in member:
+                cand[u] = k
+                k += 1
+                continue
+            g, cols = member[c]
+            if g not in gids:
+                gids[g] = len(plain) + len(gcols)
+                gcols.append((torch.as_tensor(cols, device=device), c))
+            cand[u] = gids[g]
+        plain_col = torch.as_tensor(plain + [-1] * len(gcols), dtype=torch.long, device=device)
+        return torch.as_tensor(cand, device=device), plain_col, gcols
+
+    def _shap_block(self, X: torch.Tensor, hist: List[dict]):
+        """Top-K attributions of one block of records: (column [n, K] (-1 = no insight), phi [n, K, C]).
+        The selection is ``_loco_block``'s -- top-K positive and negative candidates by the selecting score
+        column, merged by one stable sort -- except that a candidate whose attribution is 0 in the selecting
+        column but not in another one (a column only another class's trees split on) counts as a positive
+        of strength 0, so that all insights of a record still add up to its score."""
+        n = X.shape[0]
+        dev = X.device
+        phi, used = self._shap(X)
+        U, C = phi.shape[1] - 1, phi.shape[2]
+        if C == 1:
+            ex = torch.zeros(n, dtype=torch.long, device=dev)
+        elif C == 2:
+            ex = torch.ones(n, dtype=torch.long, device=dev)
+        else:
+            learner, state = self._learner_state()
+            ex = learner.predict(state, X)[0].reshape(-1).to(torch.long)
+        cand, plain_col, gcols = self._shap_plan(hist, used, dev)
+        m = int(plain_col.numel())
+        k = int(self.params["top_k"])
+        abs_mode = self.params["top_k_strategy"] == "abs"
+        kk = min(k, m)
+        K = min(k if abs_mode else 2 * k, 2 * kk)
+        if m == 0 or n == 0:
+            return (torch.full((n, K), -1, dtype=torch.long, device=dev),
+                    torch.zeros(n, K, C, dtype=torch.float64, device=dev))
+        V = torch.zeros(n, m, C, dtype=torch.float64, device=dev)
+        V.index_add_(1, cand, phi[:, :U])
+        Cc = plain_col[None, :].expand(n, m).clone()
+        n_plain = m - len(gcols)
+        for g, (gct, first_used) in enumerate(gcols):
+            active = X[:, gct] != 0
+            Cc[:, n_plain + g] = torch.where(active.any(1), gct[active.to(torch.int8).argmax(1)],
+                                             torch.full((n,), first_used, dtype=torch.long, device=dev))
+        val = V.gather(2, ex.view(n, 1, 1).expand(n, m, 1)).squeeze(2)
+        valid = (V != 0).any(2)
+        ninf = torch.full_like(val, -float("inf"))
+        pv, pi = torch.topk(torch.where(valid & (val >= 0), val, ninf), kk, dim=1)
+        nv, ni = torch.topk(torch.where(valid & (val < 0), -val, ninf), kk, dim=1)
+        idx = torch.cat([pi, ni], 1)                                   # positives first, then negatives
+        ok = torch.cat([pv, nv], 1) != -float("inf")
+        v = val.gather(1, idx)
+        key = torch.where(ok, v.abs() if abs_mode else v, torch.full_like(v, -float("inf")))
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :K]
+        sel = idx.gather(1, order)
+        okK = ok.gather(1, order)
+        colsK = torch.where(okK, Cc.gather(1, sel), torch.full_like(sel, -1))
+        diffsK = V.gather(1, sel[:, :, None].expand(n, K, C))
+        return colsK, diffsK
+
+    def bias(self, X: torch.Tensor) -> torch.Tensor:
+        """The attribution's bias per score column, ``[C]``: what the insights of a record add up from."""
+        return self._shap(X[:1])[0][0, -1]
+
+    def _run(self, X: torch.Tensor, hist: List[dict]):
+        n, d = X.shape
+        learner, state = self._learner_state()
+        # [block, U + 1, C] stays bounded: U <= d, C <= the class count (2 score columns for a binary model)
+        block = max(64, (1 << 23) // ((d + 1) * max(2, int(learner.n_classes(state)))))
+        parts = [self._shap_block(X[a:a + block], hist) for a in range(0, n, block)] or \
+            [self._shap_block(X[:0], hist)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def transform_columns(self, *cols, ds=None):
+        vec: VectorColumn = cols[0]
+        if vec.metadata is not None:
+            self.histories = vec.metadata.column_history()
+        hist = self.histories
+        if hist is None:
+            raise ValueError("RecordInsightsSHAP needs the input vector metadata (column histories)")
+        cidx, diffs = self._run(vec.values, hist)
+        return InsightsColumn(cidx, diffs, [_history_json(h) for h in hist])
+
+    def transform_row(self, *values):
+        x = torch.as_tensor(np.asarray(values[0], np.float64))[None, :]
+        if self.histories is None:
+            raise ValueError("RecordInsightsSHAP has not seen vector metadata yet")
+        cidx, diffs = self._shap_block(x, self.histories)
+        return InsightsColumn(cidx, diffs, [_history_json(h) for h in self.histories]).row(0)
 
 
 # ---------------------------------------------------------------------------------------------- Corr
