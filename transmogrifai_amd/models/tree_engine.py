@@ -31,15 +31,8 @@ MODE_CLS, MODE_VAR, MODE_GH = 0, 1, 2
 KIND_GINI, KIND_ENTROPY, KIND_VARIANCE, KIND_NEWTON = 0, 1, 2, 3
 KINDS = {"gini": KIND_GINI, "entropy": KIND_ENTROPY, "variance": KIND_VARIANCE, "newton": KIND_NEWTON}
 
-HIST_ITEM = np.dtype([("node", "<i4"), ("fg0", "<i4"), ("nf", "<i4"), ("excl", "<i4"),
-                      ("begin", "<i8"), ("count", "<i8")])
-PART_ITEM = np.dtype([("node", "<i4"), ("pad", "<i4"), ("begin", "<i8"), ("count", "<i8"),
-                      ("out_left", "<i8"), ("out_right", "<i8")])
-LEAF_ITEM = np.dtype([("begin", "<i8"), ("count", "<i8"), ("out", "<i8"), ("gid", "<i4"), ("pad", "<i4")])
-assert HIST_ITEM.itemsize == 32 and PART_ITEM.itemsize == 40 and LEAF_ITEM.itemsize == 32
-
 ROW_MASK = 0xFFFFFF
-CSR_ITEM_ROWS = 1024          # rows per CSR histogram item (tree_grow.hpp kCsrRows)
+CSR_ITEM_ROWS = N.ABI_CONSTS["TMOG_CSR_ITEM_ROWS"]    # rows per CSR histogram item
 MAX_ROWS = 1 << 24            # packed entries (row | weight << 24) below this many training rows
 MAX_WIDE_ROWS = 1 << 31       # wide entries (32-bit row id, weight 1)
 
@@ -54,7 +47,7 @@ def wide_rows(n_rows: int) -> bool:
 # running concurrently from several host threads need disjoint slot ranges. A thread running a whole learner next
 # to others (tuning/validators.py concurrent learners) takes a lane of SLOT_LANE slots; every grow_forest call of
 # that thread -- and of the threads it starts through ``set_slot_lane`` -- offsets its slot_base by the lane.
-N_SLOTS, SLOT_LANE = 32, 8
+N_SLOTS, SLOT_LANE = N.ABI_CONSTS["TMOG_N_SLOTS"], N.ABI_CONSTS["TMOG_SLOT_LANE"]
 _lane = threading.local()
 
 
@@ -356,33 +349,9 @@ def _root_rows(jobs, dev, wide: bool = False):
     return rows, counts
 
 
-class _GrowArgs(C.Structure):
-    """Mirror of ``tmog::GrowArgs`` (ops/csrc/common/tree_grow.hpp)."""
-    _fields_ = [("Xb", C.c_void_p), ("N", C.c_int64), ("F", C.c_int32), ("mode", C.c_int32), ("kind", C.c_int32),
-                ("S", C.c_int32), ("B", C.c_int32), ("missing_bin", C.c_int32), ("chunk_rows", C.c_int64),
-                ("subtract", C.c_int32), ("collect_leaves", C.c_int32), ("y", C.c_void_p), ("t1", C.c_void_p),
-                ("t2", C.c_void_p), ("stride", C.c_int64), ("qscale", C.c_void_p), ("qinv", C.c_void_p),
-                ("n_bins", C.c_void_p), ("T", C.c_int32), ("job_model", C.c_void_p), ("job_depth", C.c_void_p),
-                ("job_min_inst", C.c_void_p), ("job_min_gain", C.c_void_p), ("job_mcw", C.c_void_p),
-                ("job_lambda", C.c_void_p), ("job_eps", C.c_void_p), ("job_fsub", C.c_void_p),
-                ("job_count", C.c_void_p), ("rows", C.c_void_p), ("rows_alt", C.c_void_p),
-                ("leaf_rows", C.c_void_p), ("leaf_gid", C.c_void_p), ("n_groups", C.c_int32),
-                ("group_start", C.c_void_p), ("rng_seed", C.c_int64), ("stream", C.c_void_p),
-                ("n_bins_host", C.c_void_p), ("csr_ptr", C.c_void_p), ("csr_col", C.c_void_p),
-                ("csr_nf", C.c_int32), ("fp_rank", C.c_int32), ("fp_world", C.c_int32), ("fp_mlo", C.c_int32),
-                ("fp_mhi", C.c_int32), ("fp_olo", C.c_int32), ("fp_ohi", C.c_int32), ("fp_comm", C.c_void_p),
-                ("fp_exchange", C.c_void_p), ("fp_ctx", C.c_void_p), ("slot_base", C.c_int32),
-                ("XbT", C.c_void_p), ("gh", C.c_void_p), ("gh_alt", C.c_void_p), ("n_entries", C.c_int64),
-                ("wide_rows", C.c_int32), ("Xh", C.c_void_p), ("Fh", C.c_int32)]
-
-
-class _ResidentIO(C.Structure):
-    """Mirror of ``ResidentIO`` (ops/csrc/hip/tree_resident.hip)."""
-    _fields_ = [("rec", C.c_void_p), ("gid_value", C.c_void_p), ("gid_tree", C.c_void_p), ("cap_nodes", C.c_int64),
-                ("job_eta", C.c_void_p), ("job_gamma", C.c_void_p)]
-
-
-REC_FIXED = 7     # record words before the S totals: tree feat bin dl gain left right (tree_resident.hip)
+# ctypes mirrors of GrowArgs / ResidentIO, derived from ops/csrc/common/tmog_abi.h; built by keyword only
+_GrowArgs, _ResidentIO = N.STRUCTS["GrowArgs"], N.STRUCTS["ResidentIO"]
+REC_FIXED = N.ABI_CONSTS["TMOG_REC_FIXED"]     # record words before the S totals: tree feat bin dl gain left right
 
 
 @dataclass
@@ -680,22 +649,26 @@ def grow_forest(Xb: torch.Tensor, n_bins: np.ndarray, jobs: Sequence[TreeJob], *
         fp_cb = None if on_gpu else fp.par.fp.exchange_fn()
     else:
         fp_comm = fp_cb = None
-    a = _GrowArgs(N.ptr(Xb), Nrows, F, mode, kind, S, B, missing_bin, int(chunk_rows), int(bool(subtract)),
-                  int(bool(collect_leaves)), N.ptr(yf), N.ptr(t1f), N.ptr(t2f), stride, N.ptr(qscale), N.ptr(qinv),
-                  N.ptr(n_bins_t), T, hp["model"], hp["depth"], hp["inst"], hp["gain"], hp["mcw"], hp["lam"], hp["eps"],
-                  hp["fsub"], hp["count"], N.ptr(rows), N.ptr(rows_alt), N.ptr(leaf_rows), N.ptr(leaf_gid), ng,
-                  hp["cuts"], int(rng_seed), N.stream(dev) if on_gpu else None,
-                  hp["nbins"] if (fpw > 0 or os.environ.get("TMOG_TREE_PERM") != "0") else None,
-                  N.ptr(csr[0]) if use_csr else None, N.ptr(csr[1]) if use_csr else None,
-                  int(csr[2]) if use_csr else 0,
-                  int(fp.par.rank) if fpw else 0, fpw, fp.mlo if fpw else 0, fp.mhi if fpw else 0,
-                  fp.olo if fpw else 0, fp.ohi if fpw else 0,
-                  C.cast(fp_comm, C.c_void_p) if fp_comm is not None else None,
-                  C.cast(fp_cb, C.c_void_p) if fp_cb is not None else None, None, int(slot_base),
-                  N.ptr(XbT) if (on_gpu and XbT is not None) else None,
-                  N.ptr(gh) if gh is not None else None, N.ptr(gh_alt) if gh_alt is not None else None, total,
-                  int(wide), N.ptr(Xh) if (on_gpu and Xh is not None) else None,
-                  int(Xh.shape[1]) if (on_gpu and Xh is not None) else 0)
+    a = _GrowArgs(
+        Xb=N.ptr(Xb), N=Nrows, F=F, mode=mode, kind=kind, S=S, B=B, missing_bin=missing_bin,
+        chunk_rows=int(chunk_rows), subtract=int(bool(subtract)), collect_leaves=int(bool(collect_leaves)),
+        y=N.ptr(yf), t1=N.ptr(t1f), t2=N.ptr(t2f), stride=stride, qscale=N.ptr(qscale), qinv=N.ptr(qinv),
+        n_bins=N.ptr(n_bins_t), T=T, job_model=hp["model"], job_depth=hp["depth"], job_min_inst=hp["inst"],
+        job_min_gain=hp["gain"], job_mcw=hp["mcw"], job_lambda=hp["lam"], job_eps=hp["eps"], job_fsub=hp["fsub"],
+        job_count=hp["count"], rows=N.ptr(rows), rows_alt=N.ptr(rows_alt), leaf_rows=N.ptr(leaf_rows),
+        leaf_gid=N.ptr(leaf_gid), n_groups=ng, group_start=hp["cuts"], rng_seed=int(rng_seed),
+        stream=N.stream(dev) if on_gpu else None,
+        n_bins_host=hp["nbins"] if (fpw > 0 or os.environ.get("TMOG_TREE_PERM") != "0") else None,
+        csr_ptr=N.ptr(csr[0]) if use_csr else None, csr_col=N.ptr(csr[1]) if use_csr else None,
+        csr_nf=int(csr[2]) if use_csr else 0,
+        fp_rank=int(fp.par.rank) if fpw else 0, fp_world=fpw, fp_mlo=fp.mlo if fpw else 0,
+        fp_mhi=fp.mhi if fpw else 0, fp_olo=fp.olo if fpw else 0, fp_ohi=fp.ohi if fpw else 0,
+        fp_comm=C.cast(fp_comm, C.c_void_p) if fp_comm is not None else None,
+        fp_exchange=C.cast(fp_cb, C.c_void_p) if fp_cb is not None else None, fp_ctx=None,
+        slot_base=int(slot_base), XbT=N.ptr(XbT) if (on_gpu and XbT is not None) else None,
+        gh=N.ptr(gh) if gh is not None else None, gh_alt=N.ptr(gh_alt) if gh_alt is not None else None,
+        n_entries=total, wide_rows=int(wide), Xh=N.ptr(Xh) if (on_gpu and Xh is not None) else None,
+        Fh=int(Xh.shape[1]) if (on_gpu and Xh is not None) else 0)
     lib = N.hip() if on_gpu else N.host()
     if resident and on_gpu and ng == 1 and collect_leaves:
         rt = _grow_resident(lib, a, jobs, mode, kind, S, missing_bin, leaf_rows, leaf_gid, dev, total, wide)
@@ -767,7 +740,8 @@ def _grow_resident(lib, a, jobs, mode, kind, S, missing_bin, leaf_rows, leaf_gid
     gid_tree = torch.empty(cap, dtype=torch.int64, device=dev)
     eta = np.ascontiguousarray([j.params.eta for j in jobs], np.float64)
     gam = np.ascontiguousarray([j.params.gamma for j in jobs], np.float64)
-    io = _ResidentIO(N.ptr(rec), N.ptr(gid_value), N.ptr(gid_tree), cap, eta.ctypes.data, gam.ctypes.data)
+    io = _ResidentIO(rec=N.ptr(rec), gid_value=N.ptr(gid_value), gid_tree=N.ptr(gid_tree), cap_nodes=cap,
+                     job_eta=eta.ctypes.data, job_gamma=gam.ctypes.data)
     rc = int(lib.tmog_hip_grow_resident(C.byref(a), C.byref(io)))
     if rc == 1:
         return None
@@ -1032,7 +1006,7 @@ def _finalize_py(jobs, G: "_Nodes", mode, kind, K, S, missing_bin, with_gid_valu
     return f
 
 
-_PM_VK = 32      # tree_kernels.hip forest_predict_multi_kernel: variants x classes per model
+_PM_VK = N.ABI_CONSTS["TMOG_PM_VK"]      # tree_kernels.hip forest_predict_multi_kernel: variants x classes per model
 
 
 def _pm_lds_bytes(F: int) -> int:

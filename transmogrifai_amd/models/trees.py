@@ -783,7 +783,7 @@ def _xgb_growth_matrix(Xb, spec, dev, par):
         colperm = np.concatenate([base_perm, np.zeros(F4 - F0, np.int64)])
     # compact histogram matrix: the leading multi-bin columns of Xg at a 64-byte row stride (aligned row
     # segments, and a footprint that fits the Infinity Cache better than the full padded rows); only the
-    # wide-load histogram items read it (tree_grow.hpp GrowArgs.Xh)
+    # wide-load histogram items read it (tmog_abi.h GrowArgs.Xh)
     Xh = None
     if dev.type == "cuda" and spec.missing_bin > 0 and os.environ.get("TMOG_HIST_COMPACT", "1") != "0":
         nbg = np.asarray(n_bins_g)
@@ -796,7 +796,7 @@ def _xgb_growth_matrix(Xb, spec, dev, par):
     # one-hot / null-indicator columns: histogram from the rows' CSR lists (tree_kernels.hip)
     csr = TE.onebin_csr(Xg, n_bins_g, cols=None if fp is None else fp.one_cols) \
         if (dev.type == "cuda" and spec.missing_bin > 0) else None
-    # feature-major copy for the partition kernel's split-column reads (tree_grow.hpp GrowArgs.XbT)
+    # feature-major copy for the partition kernel's split-column reads (tmog_abi.h GrowArgs.XbT)
     XgT = Xg.t().contiguous() if (dev.type == "cuda" and os.environ.get("TMOG_PART_T", "1") != "0") else None
     return Xg, n_bins_g, colperm, Xh, fp, csr, XgT
 

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 import torch
@@ -26,138 +27,69 @@ I32 = C.c_int32
 I64 = C.c_int64
 F32 = C.c_float
 
-_HOST_SIGS = {
-    "tmog_tree_finalize_cpu": [I64, I32, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P,
-                               P, P],
-    "tmog_hist_build_cpu": [P, I64, I32, P, I32, P, P, P, P, P, P, P, P, I32, I32, I32, P, P, P, I64, P, I32],
-    "tmog_split_find_cpu": [P, I32, P, P, P, P, P, I32, I32, I32, P, I32, P, P, P, P, P, P, P, P, P, I64, I32, I32,
-                            I32],
-    "tmog_partition_cpu": [P, I32, P, P, I32, P, P, P, P, P, I32, P, P, I32],
-    "tmog_forest_predict_cpu": [P, I32, I32, P, P, P, P, P, P, P, I32, P, I32, P],
-    "tmog_forest_shap_cpu": [P, I32, I64, P, I32, P, I64, P, P, P, I32, P, P, P, P, P, I32, I32, C.c_double, P],
-    "tmog_find_splits_cpu": [P, I64, I32, I32, P, P],
-    "tmog_murmur3_batch": [P, P, I64, I32, P],
-    "tmog_hash_index_batch": [P, P, I64, I32, I32, P],
-    "tmog_col_stats_cpu": [P, P, I64, I32, I64, P],
-    "tmog_grow_forest_cpu": [P],
-    "tmog_grow_status_cpu": [P, P, I32],
-    "tmog_grow_nodes_cpu": [P, I32],
-    "tmog_grow_leaf_count_cpu": [P, I32],
-    "tmog_grow_copy_cpu": [P, I32, P, P, P, P, P, P, P, P],
-    "tmog_grow_free_cpu": [P],
-    "tmog_shist_new": [I32, I32, I64],
-    "tmog_shist_free": [P],
-    "tmog_shist_update": [P, P, P, I64],
-    "tmog_shist_flush": [P],
-    "tmog_shist_merge": [P, P],
-    "tmog_shist_size": [P],
-    "tmog_shist_bins": [P, P, P],
-    "tmog_shist_sum": [P, C.c_double],
-    "tmog_tok_run": [P, P, I64, I32, I32, I32],
-    "tmog_tok_sizes": [P, P, P],
-    "tmog_tok_copy": [P, P, P, P, P],
-    "tmog_tok_free": [P],
-    "tmog_clean_ascii_lens": [P, P, I64, P, P, P],
-    "tmog_first_ids": [P, P, P, I64, P],
-}
-
-_HIP_SIGS = {
-    "tmog_hip_hist_build": [P, I32, P, P, I32, P, P, P, P, P, I32, I32, I32, P, P, P, I64, P, I32, P, P, I32, I32, I32, P,
-                            P, P, I32, P, I32],
-    "tmog_hip_hist_stat_chunk": [I32, I32],
-    "tmog_hip_hist_subtract": [P, P, P, P, P, P, I32, I64, I64, I32, I32, P],
-    "tmog_hip_split_find": [P, I32, P, P, P, P, P, I32, I32, I32, P, I32, P, P, I32, P, P, P, P, P, P, P, P, I32, P,
-                            I64, I32, I32, I32, P, P, P],
-    "tmog_hip_fp_merge": [P, I32, I32, I64, I32, P, P, P, P, P, P],
-    "tmog_hip_rccl_unique_id": [P, I32],
-    "tmog_hip_rccl_comm_init": [P, I32, I32],
-    "tmog_hip_rccl_comm_destroy": [P],
-    "tmog_hip_partition_fused": [P, I32, P, P, P, I32, P, P, P, P, P, P, P, I32, P, P, I64, P, P, P, P, I32],
-    "tmog_hip_leaf_collect": [P, P, I32, P, P, P, P, P],
-    "tmog_hip_grow_forest": [P],
-    "tmog_hip_grow_resident": [P, P],
-    "tmog_hip_resident_cap_nodes": [P],
-    "tmog_hip_resident_error": [P, I32],
-    "tmog_hip_grow_status": [P, P, I32],
-    "tmog_hip_grow_nodes": [P, I32],
-    "tmog_hip_grow_leaf_count": [P, I32],
-    "tmog_hip_grow_copy": [P, I32, P, P, P, P, P, P, P, P],
-    "tmog_hip_grow_free": [P],
-    "tmog_hip_zero_segments": [P, P, P, I32, I64, I64, I32, I32, P, I32, P],
-    "tmog_hip_grow_timing": [P, I32],
-    "tmog_hip_boost_epilogue": [P, P, I64, P, P, P, I64, P, P, P, P, I32, P, I32, I64, I64, I64, P, P, I32],
-    "tmog_hip_boost_margin_add": [P, P, I64, P, P, P, I64, P, I64, I64, I64, I32, P],
-    "tmog_hip_softmax_grad": [P, P, P, I32, I64, I32, I64, I64, P, P, P, P, P, P, P],
-    "tmog_hip_aupr_counts": [P, I32, I32, P, P],
-    "tmog_hip_slot_stream": [I32, P, I32],
-    "tmog_hip_lr_blocks_per_cu": [I32],
-    "tmog_hip_plan_profile": [P, I32],
-    "tmog_hip_masked_colsum": [P, P, P, I32, I64, I64, P, P],
-    "tmog_hip_wgram": [P, I64, I32, I64, P, I64, I32, P, I64, I32, P, P],
-    "tmog_hip_weighted_colsums": [P, I64, I32, I64, P, I64, I32, P, P],
-    "tmog_hip_boost_prologue": [P, P, P, P, I32, P, I32, P, P, P, I64, P, P, I64, P, P, P, C.c_float, I32, P],
-    "tmog_hip_owlqn_direction": [P, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P],
-    "tmog_hip_owlqn_candidate": [P, P, P, P, P, P, I32, I32, P, P, P, P],
-    "tmog_hip_poisson_pack": [P, I64, P, I32, P, I32, P, P, P, P],
-    "tmog_hip_row_uniform": [P, I64, P, I32, P, P],
-    "tmog_hip_lr_objective": [P, I64, I32, P, P, I32, I32, I32, P, P, I32, P, I32, P, P, P, I32, P],
-    "tmog_hip_lr_objective_mixed": [P, I64, I32, P, I32, I32, P, P, I32, I32, I32, P, P, I32, P, I32, P, P, P, I32,
-                                    P],
-    "tmog_hip_lr_epilogue_grad": [P, I64, I32, P, P, P, I32, I32, I32, P, I32, P, I32, P, P, P, I32, P],
-    "tmog_hip_forest_predict": [P, I32, I32, P, P, I64, P, P, P, P, P, I32, P, I32, P, P],
-    "tmog_hip_forest_predict_multi": [P, I32, I32, P, P, I64, P, P, P, P, P, I32, P, I32, P, P, P, P, P, P],
-    "tmog_hip_forest_shap": [P, I32, I64, P, I32, P, I64, P, P, P, I32, P, P, P, P, P, I32, I32, C.c_double, P, P],
-    "tmog_hip_col_stats": [P, P, I64, I32, I64, P, P],
-    "tmog_hip_vectorize_numeric": [P, P, P, I64, I32, P, P, P, P, I64, I32, P],
-    "tmog_hip_onehot_pivot": [P, P, P, P, I32, I64, P, I64, P],
-    "tmog_hip_quantize": [P, I64, I32, P, I32, I32, I32, F32, P, P],
-    "tmog_hip_gram_aug": [P, I64, I32, I64, P, P, I32, P, P],
-    "tmog_hip_gram_bf16": [P, I64, I64, I32, P, P],
-    "tmog_hip_col_bf16_exact": [P, I64, I32, I64, P, P],
-    "tmog_hip_bf16_pack": [P, I64, I64, P, P, P, P, P, P, I64, P],
-    "tmog_hip_class_colsum": [P, I64, I32, I64, P, I32, I32, P, P],
-    "tmog_hip_logistic_grad": [P, P, P, I64, I32, P],
-    "tmog_hip_debug_flags": [I32],
-    "tmog_hip_csr_spmm": [P, P, P, I64, P, I32, P, I32, I32, P],
-    "tmog_hip_csc_spmm_t": [P, P, P, I64, P, I64, P, I32, I32, P, P, P],
-    "tmog_hip_softmax_epilogue": [P, I64, I32, I32, P, P, P, I32, P, I32, P],
-    "tmog_hip_colsum": [P, I64, I32, I32, P, P],
-    "tmog_hip_mlp_bias_sigmoid": [P, I32, I64, I32, P, P],
-    "tmog_hip_mlp_sigmoid_backprop": [P, P, I32, I64, I32, I32, P, P],
-    "tmog_hip_gather_rows_cols": [P, P, P, I64, I32, P, P],
-    "tmog_hip_hash_tokens": [P, P, I64, P, I32, I32, I32, I32, P, P],
-    "tmog_hip_hash_tf_rows": [P, I32, I64, I32, I32, P, I64, I64, P],
-    "tmog_hip_hash_feat_bytes": [],
-    "tmog_hip_code_count": [P, P, I32, I32, I64, P, P],
-    "tmog_hip_bucketize": [P, P, I64, P, I32, I32, I32, I32, P, I64, I64, I32, P, P],
-    "tmog_hip_date_unit_circle": [P, P, I64, I32, I32, I32, P, I64, I64, P],
-    "tmog_hip_rff_summary": [P, P, P, I64, I32, P, I32, P, P],
-    "tmog_hip_rff_hist": [P, P, P, I64, I32, P, P, I32, P, P],
-    "tmog_hip_binary_areas": [P, I32, P, I64, I32, P, P, P, P],
-    "tmog_hip_lr_bf16_blocks_per_cu": [I32, I32],
-    "tmog_hip_mnl_epilogue": [P, I64, I32, I32, P, P, P, I32, P, I32, P, P, P, I32, P],
-    "tmog_hip_mnl_bf16": [P, I64, I64, I32, P, P, I32, P, I32, I32, P, P, I32, P, P, P, I32, P],
-    "tmog_hip_lr_bf16": [P, I64, I64, I32, P, P, I32, P, I32, P, P, I32, P, I32, P, P, P, I32, P],
-    "tmog_hip_csv_fields": [P, P, P, I64, I32, I32, P, P, P],
-    "tmog_hip_rowgemm": [P, I64, I64, P, I64, I64, I32, I32, I64, P, I64, I64, P, I64, I64, I32, I64, I64, I32, I32, I32,
-                         I32, P],
-    "tmog_hip_xtd_chunks": [I64, I32, I32, I32, I32],
-    "tmog_hip_xtd": [P, I64, I64, P, I64, I64, I32, I64, I64, I32, I32, I32, I32, P, P, P],
-    "tmog_hip_csv_parse_num": [P, P, P, I64, I32, P, P, I32, P, P, P, P],
-    "tmog_hip_csv_hash_text": [P, P, P, I64, I32, P, I32, P, P, P, P],
-}
+# ---- the native ABI, read from the two headers that are its only declaration (csrc/common/tmog_abi.h,
+# csrc/hip/tmog_hip_abi.h). The headers keep to a restricted style, so this is a reader, not a C parser.
+_SCALARS = {"int": I32, "int32_t": I32, "unsigned": I32, "uint32_t": I32, "int64_t": I64, "uint64_t": I64,
+            "size_t": C.c_size_t, "long": C.c_long, "float": F32, "double": C.c_double}
 
 
-_RESTYPES = {"tmog_tok_run": C.c_void_p, "tmog_tok_sizes": None, "tmog_tok_copy": None, "tmog_tok_free": None, "tmog_hip_grow_timing": None, "tmog_clean_ascii_lens": None, "tmog_first_ids": I64,
-             "tmog_tree_finalize_cpu": C.c_int64, "tmog_shist_new": C.c_void_p, "tmog_shist_free": None, "tmog_shist_update": None,
-             "tmog_shist_flush": None, "tmog_shist_merge": None, "tmog_shist_bins": None,
-             "tmog_shist_size": C.c_int64, "tmog_shist_sum": C.c_double,
-             "tmog_hip_split_cand_bytes": C.c_size_t, "tmog_hip_rccl_comm_init": C.c_void_p,
-             "tmog_grow_forest_cpu": C.c_void_p, "tmog_hip_grow_forest": C.c_void_p,
-             "tmog_grow_nodes_cpu": C.c_int64, "tmog_hip_grow_nodes": C.c_int64,
-             "tmog_grow_leaf_count_cpu": C.c_int64, "tmog_hip_grow_leaf_count": C.c_int64,
-             "tmog_grow_copy_cpu": None, "tmog_hip_grow_copy": None,
-             "tmog_grow_free_cpu": None, "tmog_hip_grow_free": None, "tmog_hip_resident_cap_nodes": C.c_int64}
+def _ctype(decl: str, named: bool = True):
+    """ctypes type of one C declarator: ``const float* y`` / ``int64_t N``, or a bare return type."""
+    if "*" in decl or decl.split()[0] == "hipStream_t":
+        return P
+    words = [w for w in decl.split() if w != "const"]
+    base = " ".join(words[:-1] if named else words)
+    if base == "void" and not named:
+        return None
+    if base not in _SCALARS:
+        raise ValueError(f"native ABI header: unknown type in {decl.strip()!r}")
+    return _SCALARS[base]
+
+
+def parse_abi(text: str):
+    """``(functions, structs, defines)`` of an ABI header: ``{name: (restype, [argtypes])}``,
+    ``{struct: [(field, ctype)]}`` and ``{NAME: int}``."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r"\(\s*\*\s*(\w+)\s*\)\s*\([^()]*\)", r"* \1", text)     # a function pointer is a pointer
+    structs = {}
+    for m in re.finditer(r"struct\s+(\w+)\s*\{([^{}]*)\}", text):
+        fields = structs[m[1]] = []
+        for decl in filter(str.strip, m[2].split(";")):
+            names = [n.split()[-1] for n in decl.split(",")]        # `int32_t F, mode, kind`: one type, many names
+            if "*" in decl and len(names) > 1:
+                raise ValueError(f"native ABI header: one pointer per declaration, got {decl.strip()!r}")
+            fields += [(n, _ctype(decl.split(",")[0])) for n in names]
+    text = re.sub(r"struct\s+\w+\s*\{[^{}]*\}", "", text)
+    funcs = {}
+    for m in re.finditer(r"([\w\s\*]+?)\b(tmog_\w+)\s*\(([^();]*)\)\s*;", text):
+        if m[2] in funcs:
+            raise ValueError(f"native ABI header: {m[2]} declared twice")
+        funcs[m[2]] = (_ctype(m[1], named=False), [_ctype(a) for a in m[3].split(",") if a.strip() not in ("", "void")])
+    return funcs, structs, defines
+
+
+_HOST_ABI, _STRUCT_FIELDS, ABI_CONSTS = parse_abi((build.CSRC / "common" / "tmog_abi.h").read_text())
+_HIP_ABI = parse_abi((build.CSRC / "hip" / "tmog_hip_abi.h").read_text())[0]
+_HOST_SIGS = {name: args for name, (_, args) in _HOST_ABI.items()}
+_HIP_SIGS = {name: args for name, (_, args) in _HIP_ABI.items()}
+_RESTYPES = {name: res for name, (res, _) in {**_HOST_ABI, **_HIP_ABI}.items()}
+
+
+class _Struct(C.Structure):
+    """A mirror of a struct of ``tmog_abi.h``; built by keyword, every field named exactly once."""
+
+    def __init__(self, **kw):
+        names = {f for f, _ in self._fields_}
+        if names != set(kw):
+            raise TypeError(f"{type(self).__name__}: missing {sorted(names - set(kw))}, "
+                            f"unknown {sorted(set(kw) - names)}")
+        super().__init__(**kw)
+
+
+STRUCTS = {name: type(name, (_Struct,), {"_fields_": fields}) for name, fields in _STRUCT_FIELDS.items()}
+_SIZEOF_ORDER = ("GrowArgs", "ResidentIO", "HistItem", "PartItem", "LeafItem")     # tmog_abi_sizeof(which)
 
 
 def _declare(lib, sigs):
@@ -166,7 +98,7 @@ def _declare(lib, sigs):
         if fn is None:
             continue
         fn.argtypes = args
-        fn.restype = _RESTYPES.get(name, C.c_int)
+        fn.restype = _RESTYPES[name]
 
 
 def _check_loaded_hash(lib, kind: str) -> None:
@@ -189,6 +121,10 @@ def host():
                 lib = C.CDLL(str(path))
                 _declare(lib, _HOST_SIGS)
                 _check_loaded_hash(lib, "host")
+                for which, name in enumerate(_SIZEOF_ORDER):       # the compiler's layout against the derived mirrors
+                    if lib.tmog_abi_sizeof(which) != C.sizeof(STRUCTS[name]):
+                        raise RuntimeError(f"{name}: the host library has sizeof {lib.tmog_abi_sizeof(which)}, the "
+                                           f"ctypes mirror read from tmog_abi.h {C.sizeof(STRUCTS[name])}")
                 _host = lib
     return _host
 
@@ -244,10 +180,7 @@ def hip():
                 # one device-memory budget: a native buffer growth that runs out of memory first returns
                 # torch's cached-but-unused blocks to the device, then retries (ops/csrc/hip/dev_alloc.hpp)
                 lib.tmog_hip_set_oom_handler.argtypes = [_OOM_HANDLER_T]
-                lib.tmog_hip_set_oom_handler.restype = None
                 lib.tmog_hip_set_oom_handler(_OOM_HANDLER)
-                lib.tmog_hip_fail_alloc.argtypes = [C.c_long]
-                lib.tmog_hip_fail_alloc.restype = None
                 _hip = lib
     return _hip
 

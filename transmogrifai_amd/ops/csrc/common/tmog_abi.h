@@ -1,0 +1,220 @@
+// The C ABI of libtmog_host.so, and the structs and constants both native libraries share with Python.
+//
+// This header is the ONLY declaration of these entry points. Every host translation unit includes it, so the
+// compiler checks each definition against it (a conflicting extern "C" redeclaration is an error), and
+// ops/_native.py reads it to derive the ctypes signatures, struct layouts and constants -- nothing is retyped.
+//
+// Restricted style, so that the small reader in ops/_native.py stays a reader and not a C parser: plain C, one
+// declaration per ';', every parameter named, only fixed-width / builtin scalar types and pointers, no macros or
+// default arguments inside parameter lists, constants as `#define NAME integer`. Comments are free.
+// (The two CPython-API functions of host/utf8_pack.cpp take PyObject* and stay declared where they are loaded.)
+#pragma once
+
+#include <assert.h>
+#include <stddef.h>
+#include <stdint.h>
+
+// ---- constants mirrored by Python (models/tree_engine.py reads them from here)
+#define TMOG_N_SLOTS 32            // native per-group resource slots of the GPU grower (tree_grow_hip.hip slots())
+#define TMOG_SLOT_LANE 8           // slots one concurrently running learner thread owns
+#define TMOG_REC_FIXED 7           // resident record words before the S totals: tree feat bin dl gain left right
+#define TMOG_CSR_ITEM_ROWS 1024    // rows per CSR histogram item (GPU)
+#define TMOG_PART_ITEM_ROWS 1024   // rows per partition item (GPU)
+#define TMOG_PM_VK 32              // forest_predict_multi_kernel: variants x classes accumulated per thread
+
+// ---- work items of the tree level kernels (hip/tree_kernels.hip), planned by common/tree_grow.hpp on the host
+// and by hip/tree_resident.hip on the device
+typedef struct HistItem {
+  int32_t node;     // node slot
+  int32_t fg0;      // first local feature of this group
+  int32_t nf;       // features in this group (<= 64)
+  int32_t excl;     // bit 0: this item alone covers node rows for its features (plain stores)
+                    // bit 1: every feature of the group has one present bin (register accumulation)
+                    // bit 2: CSR item, bit 3: only the bin-0 words of each feature are written out,
+                    // bit 4: wide-load item, bits 8..15: statistic chunk
+  int64_t begin;    // first row entry
+  int64_t count;    // row entries in this chunk
+} HistItem;
+
+typedef struct PartItem {
+  int32_t node;
+  int32_t pad;
+  int64_t begin;      // absolute position of the chunk in rows_in
+  int64_t count;
+  int64_t out_left;   // absolute output position for this chunk's first left row
+  int64_t out_right;  // absolute output position for this chunk's first right row
+} PartItem;
+
+typedef struct LeafItem {
+  int64_t begin;    // first entry in rows
+  int64_t count;
+  int64_t out;      // output position
+  int32_t gid;      // node id
+  int32_t buf;      // row buffer: 0 = rows, 1 = rows_alt (device-planned levels collect from both)
+} LeafItem;
+
+static_assert(sizeof(HistItem) == 32 && sizeof(PartItem) == 40 && sizeof(LeafItem) == 32, "item layout");
+
+// ---- arguments of one grower call (tmog_grow_forest_cpu / tmog_hip_grow_forest / tmog_hip_grow_resident)
+typedef struct GrowArgs {
+  const uint8_t* Xb;
+  int64_t N;
+  int32_t F, mode, kind, S, B, missing_bin;
+  int64_t chunk_rows;
+  int32_t subtract, collect_leaves;
+  const float* y;
+  const float* t1;
+  const float* t2;
+  int64_t stride;
+  const float* qscale;
+  const double* qinv;
+  const int32_t* n_bins;
+  int32_t T;
+  const int32_t* job_model;
+  const int32_t* job_depth;
+  const double* job_min_inst;
+  const double* job_min_gain;
+  const double* job_mcw;
+  const double* job_lambda;
+  const double* job_eps;
+  const int32_t* job_fsub;
+  const int64_t* job_count;   // root entries per job (job-major in rows)
+  uint32_t* rows;             // packed root entries (device / host), overwritten
+  uint32_t* rows_alt;         // scratch of the same size
+  uint32_t* leaf_rows;        // collect_leaves: final leaf of every entry (same size as rows)
+  int32_t* leaf_gid;
+  int32_t n_groups;
+  const int32_t* group_start;  // [n_groups + 1] job boundaries
+  int64_t rng_seed;
+  void* stream;               // GPU: caller's stream (groups wait on it; it waits on the groups)
+  const int32_t* n_bins_host; // host copy of n_bins (feature grouping for the histogram kernel), may be null
+  // GPU, sparse missing bin: CSR of the one-present-bin columns (row -> local ids, in n_bins order, of
+  // the columns whose bin is the present bin 0); null when absent
+  const int64_t* csr_ptr;     // [N + 1]
+  const uint16_t* csr_col;
+  int32_t csr_nf;             // number of one-present-bin columns the CSR indexes
+  // Feature-parallel growth (fp_world > 0; jobs without per-node feature subsets). Every rank runs the
+  // same jobs on the same replicated rows and binned matrix but builds histograms and scans splits for
+  // its own slice of the growth-order feature list only: positions [fp_mlo, fp_mhi) of the multi-bin
+  // list and [fp_olo, fp_ohi) of the one-present-bin list (all features count as multi-bin outside the
+  // sparse missing-bin mode). Per level the ranks all-gather one split record per node (fp_rec_bytes)
+  // and every rank merges them with the split scan's total order, so all ranks partition identically
+  // and the forests equal the single-rank ones bit for bit.
+  int32_t fp_rank, fp_world;
+  int32_t fp_mlo, fp_mhi, fp_olo, fp_ohi;
+  void* const* fp_comm;       // GPU: one RCCL communicator per job group
+  int (*fp_exchange)(void* ctx, int group, const void* send, void* recv, int64_t bytes);   // CPU all-gather
+  void* fp_ctx;
+  // GPU: first per-group resource slot (stream, staging, histogram buffers) of this call -- concurrent
+  // calls (e.g. the XGBoost learner's pipelined job halves, one host thread each) use disjoint slots
+  int32_t slot_base;
+  // GPU, optional: feature-major copy of Xb ([F][N], row index = packed entry & 0xFFFFFF). The partition
+  // reads one split-column byte per row; from the feature-major copy the bytes of a node's rows share
+  // cache lines (from Xb every byte pulls its own line)
+  const uint8_t* XbT;
+  // GPU, MODE 2, optional: the entries' quantised statistics (int32 pairs q(w g), q(w h)), one per entry of
+  // rows / rows_alt (same positions); the partition moves them with their entries so the histogram items
+  // read them coalesced instead of gathering t1 / t2 by row id. n_entries = size of rows (and of these).
+  int32_t* gh;
+  int32_t* gh_alt;
+  int64_t n_entries;
+  // training sets of >= 2^24 rows: entries are plain 32-bit row ids of weight 1 instead of row | weight << 24
+  // (weighted roots are expanded into repeated entries by the caller, models/tree_engine.py)
+  int32_t wide_rows;
+  // GPU, optional: row-major matrix the wide-load histogram items read instead of Xb -- the multi-bin columns
+  // only (their Xb column positions), row stride Fh bytes (a multiple of 64: every row segment starts a cache
+  // line and the matrix is smaller than Xb, so more of it stays in the Infinity Cache). Groups whose columns
+  // reach past Fh stay on Xb.
+  const uint8_t* Xh;
+  int32_t Fh;
+} GrowArgs;
+
+// ---- outputs of one device-planned tree (tmog_hip_grow_resident)
+typedef struct ResidentIO {
+  int64_t* rec;          // [1 + cap_nodes][7 + S] int64: header (nodes, leaf entries, error bits), then node records
+  float* gid_value;      // [cap_nodes] leaf output per created node id (pruning applied)
+  int64_t* gid_tree;     // [cap_nodes] job of each created node
+  int64_t cap_nodes;
+  const double* job_eta;    // [T]
+  const double* job_gamma;  // [T]
+} ResidentIO;
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+// sizeof of the shared structs as the compiler laid them out: 0 GrowArgs, 1 ResidentIO, 2 HistItem, 3 PartItem,
+// 4 LeafItem (-1 otherwise). ops/_native.py compares them with its derived ctypes mirrors when the library loads.
+int64_t tmog_abi_sizeof(int which);
+
+// ---- host/hashing_cpu.cpp
+int tmog_murmur3_batch(const uint8_t* bytes, const int64_t* offsets, int64_t n, int32_t seed, int32_t* out);
+int tmog_hash_index_batch(const uint8_t* bytes, const int64_t* offsets, int64_t n, int32_t seed, int32_t num_features,
+                          int32_t* out);
+
+// ---- host/streaming_histogram.cpp
+void* tmog_shist_new(int max_bins, int max_spool, int64_t round_to);
+void tmog_shist_free(void* h);
+void tmog_shist_update(void* h, const double* p, const int64_t* m, int64_t n);
+void tmog_shist_flush(void* h);
+void tmog_shist_merge(void* h, void* other);
+int64_t tmog_shist_size(void* h);
+void tmog_shist_bins(void* h, double* points, int64_t* counts);
+double tmog_shist_sum(void* h, double b);
+
+// ---- host/text_clean.cpp
+void tmog_clean_ascii_lens(const uint8_t* buf, const int64_t* offs, int64_t n, uint8_t* out, int64_t* lens,
+                           uint8_t* fallback);
+int64_t tmog_first_ids(const uint8_t* buf, const int64_t* starts, const int64_t* ends, int64_t n, int64_t* ids);
+
+// ---- host/tokenizer.cpp
+void* tmog_tok_run(const uint8_t* bytes, const int64_t* offs, int64_t n, int32_t lowercase, int32_t min_len,
+                   int32_t use_stop);
+void tmog_tok_sizes(void* h, int64_t* n_tokens, int64_t* n_bytes);
+void tmog_tok_copy(void* h, uint8_t* bytes, int64_t* tok_offs, int64_t* row_ptr, uint8_t* fallback);
+void tmog_tok_free(void* h);
+
+// ---- host/tree_cpu.cpp: host twins of the tree kernels (bit-identical results)
+int tmog_hist_build_cpu(const uint8_t* Xb, int64_t N, int F, const uint32_t* rows, int n_nodes,
+                        const int64_t* node_begin, const int64_t* node_count, const int32_t* node_feat_off,
+                        const int32_t* node_nfeat, const int32_t* feat_list, const int32_t* node_model,
+                        const int64_t* node_hist_off, int64_t* hist, int B, int mode, int S, const float* y,
+                        const float* t1, const float* t2, int64_t model_stride, const float* qscale, int wide);
+int tmog_split_find_cpu(const int64_t* hist, int n_nodes, const int64_t* node_hist_off, const int32_t* node_nfeat,
+                        const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B,
+                        int S, int kind, const float* node_params, int missing_bin, const int32_t* node_model,
+                        const double* qinv, int32_t* out_feat, int32_t* out_bin, float* out_gain,
+                        uint8_t* out_default_left, float* out_left, float* out_total, uint8_t* rec, int64_t rec_bytes,
+                        int fp_mlo, int fp_nml, int fp_obase);
+int tmog_partition_cpu(const uint8_t* Xb, int F, const uint32_t* rows_in, uint32_t* rows_out, int n_nodes,
+                       const int64_t* node_begin, const int64_t* node_count, const int32_t* split_feat,
+                       const int32_t* split_bin, const uint8_t* default_left, int missing_bin,
+                       const int64_t* out_begin, int64_t* out_left_count, int wide);
+int tmog_forest_predict_cpu(const uint8_t* Xb, int F, int n_models, const int64_t* model_row_off,
+                            const int32_t* row_list, const int64_t* model_tree_off, const int64_t* tree_off,
+                            const float* tree_weight, const int32_t* nodes, const uint8_t* default_left,
+                            int missing_bin, const float* leaf_value, int K, float* out);
+int tmog_forest_shap_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
+                         int64_t P, const int64_t* p_off, const int32_t* p_out, const double* p_val, int KV,
+                         const double* bias, const int32_t* e_feat, const int32_t* e_rng, const double* e_z,
+                         const int64_t* bin_off, int missing_bin, int C, double scale, double* out);
+int tmog_find_splits_cpu(const double* sample, int64_t S, int F, int max_splits, double* out, int32_t* n_out);
+int64_t tmog_tree_finalize_cpu(int64_t n, int T, const int64_t* tree, const int64_t* feat_in, const int64_t* bin,
+                               const uint8_t* dl, const double* gain, const double* tot, int S,
+                               const int64_t* left_in, const int64_t* right_in, int mode, int kind, int K,
+                               const double* job_lam, const double* job_eta, const double* job_gamma, int with_gid,
+                               int64_t* tree_off, int32_t* nodes, uint8_t* dl_out, float* value_out, float* gain_out,
+                               float* cover_out, float* gid_value);
+
+// ---- host/tree_grow_cpu.cpp: the native grower on the CPU backend. The handle is a GrowResult
+void* tmog_grow_forest_cpu(const GrowArgs* args);
+int tmog_grow_status_cpu(void* h, char* msg, int cap);
+int64_t tmog_grow_nodes_cpu(void* h, int g);
+int64_t tmog_grow_leaf_count_cpu(void* h, int g);
+void tmog_grow_copy_cpu(void* h, int g, int64_t* tree, int64_t* feat, int64_t* bin, uint8_t* dl, double* gain,
+                        double* tot, int64_t* left, int64_t* right);
+void tmog_grow_free_cpu(void* h);
+
+#ifdef __cplusplus
+}  // extern "C"
+#endif

@@ -30,6 +30,8 @@
 #include <thread>
 #include <vector>
 
+#include "common/tmog_abi.h"
+
 namespace tmog {
 
 // Deterministic cross-group order of the feature-parallel split exchanges. Every job group grows on its
@@ -89,78 +91,7 @@ inline int fp_delay_ms(int rank, int group) {
   return (r == rank && gg == group) ? ms : 0;
 }
 
-struct GrowArgs {
-  const uint8_t* Xb;
-  int64_t N;
-  int32_t F, mode, kind, S, B, missing_bin;
-  int64_t chunk_rows;
-  int32_t subtract, collect_leaves;
-  const float* y;
-  const float* t1;
-  const float* t2;
-  int64_t stride;
-  const float* qscale;
-  const double* qinv;
-  const int32_t* n_bins;
-  int32_t T;
-  const int32_t* job_model;
-  const int32_t* job_depth;
-  const double* job_min_inst;
-  const double* job_min_gain;
-  const double* job_mcw;
-  const double* job_lambda;
-  const double* job_eps;
-  const int32_t* job_fsub;
-  const int64_t* job_count;   // root entries per job (job-major in rows)
-  uint32_t* rows;             // packed root entries (device / host), overwritten
-  uint32_t* rows_alt;         // scratch of the same size
-  uint32_t* leaf_rows;        // collect_leaves: final leaf of every entry (same size as rows)
-  int32_t* leaf_gid;
-  int32_t n_groups;
-  const int32_t* group_start;  // [n_groups + 1] job boundaries
-  int64_t rng_seed;
-  void* stream;               // GPU: caller's stream (groups wait on it; it waits on the groups)
-  const int32_t* n_bins_host; // host copy of n_bins (feature grouping for the histogram kernel), may be null
-  // GPU, sparse missing bin: CSR of the one-present-bin columns (row -> local ids, in n_bins order, of
-  // the columns whose bin is the present bin 0); null when absent
-  const int64_t* csr_ptr;     // [N + 1]
-  const uint16_t* csr_col;
-  int32_t csr_nf;             // number of one-present-bin columns the CSR indexes
-  // Feature-parallel growth (fp_world > 0; jobs without per-node feature subsets). Every rank runs the
-  // same jobs on the same replicated rows and binned matrix but builds histograms and scans splits for
-  // its own slice of the growth-order feature list only: positions [fp_mlo, fp_mhi) of the multi-bin
-  // list and [fp_olo, fp_ohi) of the one-present-bin list (all features count as multi-bin outside the
-  // sparse missing-bin mode). Per level the ranks all-gather one split record per node (fp_rec_bytes)
-  // and every rank merges them with the split scan's total order, so all ranks partition identically
-  // and the forests equal the single-rank ones bit for bit.
-  int32_t fp_rank, fp_world;
-  int32_t fp_mlo, fp_mhi, fp_olo, fp_ohi;
-  void* const* fp_comm;       // GPU: one RCCL communicator per job group
-  int (*fp_exchange)(void* ctx, int group, const void* send, void* recv, int64_t bytes);   // CPU all-gather
-  void* fp_ctx;
-  // GPU: first per-group resource slot (stream, staging, histogram buffers) of this call -- concurrent
-  // calls (e.g. the XGBoost learner's pipelined job halves, one host thread each) use disjoint slots
-  int32_t slot_base;
-  // GPU, optional: feature-major copy of Xb ([F][N], row index = packed entry & 0xFFFFFF). The partition
-  // reads one split-column byte per row; from the feature-major copy the bytes of a node's rows share
-  // cache lines (from Xb every byte pulls its own line)
-  const uint8_t* XbT;
-  // GPU, MODE 2, optional: the entries' quantised statistics (int32 pairs q(w g), q(w h)), one per entry of
-  // rows / rows_alt (same positions); the partition moves them with their entries so the histogram items
-  // read them coalesced instead of gathering t1 / t2 by row id. n_entries = size of rows (and of these).
-  int32_t* gh;
-  int32_t* gh_alt;
-  int64_t n_entries;
-  // training sets of >= 2^24 rows: entries are plain 32-bit row ids of weight 1 instead of row | weight << 24
-  // (weighted roots are expanded into repeated entries by the caller, models/tree_engine.py)
-  int32_t wide_rows;
-  // GPU, optional: row-major matrix the wide-load histogram items read instead of Xb -- the multi-bin columns
-  // only (their Xb column positions), row stride Fh bytes (a multiple of 64: every row segment starts a cache
-  // line and the matrix is smaller than Xb, so more of it stays in the Infinity Cache). Groups whose columns
-  // reach past Fh stay on Xb.
-  const uint8_t* Xh;
-  int32_t Fh;
-};
+using ::GrowArgs;   // common/tmog_abi.h
 
 // Feature-parallel split record, one per node and rank:
 //   gain f64 @0 | fpos i32 @8 (position in the full growth-order feature list, the tie-break) |
@@ -237,20 +168,10 @@ struct GrowResult {
   std::string error;
 };
 
-// item layouts shared with hip/tree_kernels.hip
-struct HistItemH {
-  int32_t node, fg0, nf, excl;
-  int64_t begin, count;
-};
-struct PartItemH {
-  int32_t node, pad;
-  int64_t begin, count, out_left, out_right;
-};
-struct LeafItemH {
-  int64_t begin, count, out;
-  int32_t gid, pad;
-};
-static_assert(sizeof(HistItemH) == 32 && sizeof(PartItemH) == 40 && sizeof(LeafItemH) == 32, "item layout");
+// work items of hip/tree_kernels.hip (common/tmog_abi.h)
+using HistItemH = ::HistItem;
+using PartItemH = ::PartItem;
+using LeafItemH = ::LeafItem;
 
 // splitmix64 stream for the per-node feature subsets (identical on both backends)
 struct SplitMix {
@@ -293,8 +214,8 @@ struct FeatGroup {
   bool wide = false;   // GPU: contiguous dword-aligned physical columns -> wide-load histogram items
 };
 
-constexpr int64_t kCsrRows = 1024;   // rows per CSR histogram item (GPU)
-constexpr int64_t kPartRows = 1024;  // rows per partition item (GPU)
+constexpr int64_t kCsrRows = TMOG_CSR_ITEM_ROWS;    // rows per CSR histogram item (GPU)
+constexpr int64_t kPartRows = TMOG_PART_ITEM_ROWS;  // rows per partition item (GPU)
 
 // n features in near-equal groups of at most 64
 inline std::vector<FeatGroup> equal_groups(int n) {
@@ -463,7 +384,7 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
         it.count = std::min(a.chunk_rows, c - o);
         it.out = leaf_pos + o;
         it.gid = (int32_t)lv_gid[i];
-        it.pad = 0;
+        it.buf = 0;
         items.push_back(it);
       }
       leaf_pos += c;

@@ -27,6 +27,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int kAmaxCopies = 64;   // boost_epilogue_kernel's per-job maxima: [kAmaxCopies][P][2] (trees.py)

@@ -24,6 +24,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int kAmaxCopies = 64;   // as boost_kernels.hip: the maxima table is [kAmaxCopies][P * K][2]

@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;

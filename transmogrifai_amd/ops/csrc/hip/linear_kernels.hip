@@ -21,6 +21,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

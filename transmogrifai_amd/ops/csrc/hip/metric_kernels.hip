@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int NT = 1024;

@@ -15,6 +15,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 __global__ void __launch_bounds__(256) mlp_bias_sigmoid_kernel(float* __restrict__ Z, int P, int64_t N, int B,

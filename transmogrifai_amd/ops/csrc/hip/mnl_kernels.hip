@@ -14,6 +14,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int NT = 256;

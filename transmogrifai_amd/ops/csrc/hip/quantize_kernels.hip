@@ -15,6 +15,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int QF = 64;     // features per block (one per lane)

@@ -15,6 +15,8 @@
 #include <stdint.h>
 #include <float.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 __device__ __forceinline__ double load_val(const void* p, int dt, int64_t i) {

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int SHAP_THREADS = 512;

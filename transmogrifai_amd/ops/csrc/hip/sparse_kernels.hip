@@ -20,6 +20,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int kMaxC = 256;     // output columns per launch (lanes x 4)

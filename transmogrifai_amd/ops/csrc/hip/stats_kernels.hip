@@ -20,6 +20,8 @@
 #include <stdint.h>
 #include <float.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 __global__ void __launch_bounds__(256) col_partials_kernel(const float* __restrict__ X, int64_t n, int d, int64_t ld,

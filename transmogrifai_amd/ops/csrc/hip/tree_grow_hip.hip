@@ -18,47 +18,7 @@
 
 #include "common/tree_grow.hpp"
 #include "hip/dev_alloc.hpp"
-
-extern "C" {
-int tmog_hip_hist_build(const uint8_t* Xb, int F, const uint32_t* rows, const void* items, int n_items,
-                        const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* node_model,
-                        const int64_t* node_hist_off, int64_t* hist, int B, int mode, int S, const float* y,
-                        const float* t1, const float* t2, int64_t stride, const float* qscale, int skip_bin,
-                        const int64_t* csr_ptr, const uint16_t* csr_col, int Sc, int n_wide, int need_general,
-                        hipStream_t stream, const int32_t* gh, const int* dcount, int wide_rows,
-                        const uint8_t* Xh, int Fh);
-int tmog_hip_hist_subtract(int64_t* hist, const int64_t* parent, const int64_t* parent_off, const int64_t* small_off,
-                           const int64_t* out_off, const int64_t* size, int n, int64_t max_size, int64_t dense,
-                           int per, int S, hipStream_t stream);
-int tmog_hip_split_find(const int64_t* hist, int n_nodes, const int64_t* node_hist_off, const int32_t* node_nfeat,
-                        const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B,
-                        int S, int kind, const float* node_params, int missing_bin, const int32_t* node_model,
-                        const double* qinv, int max_nfeat, void* cand_ws, int32_t* out_feat, int32_t* out_bin,
-                        float* out_gain, uint8_t* out_dl, float* out_left, float* out_total, int64_t* cursors, int n_multi,
-                        void* rec, int64_t rec_bytes, int fp_mlo, int fp_nml, int fp_obase, hipStream_t stream,
-                        unsigned* done, const int* dm);
-int tmog_hip_fp_merge(const void* recv, int R, int m, int64_t rec_bytes, int S, int32_t* out_feat, int32_t* out_bin,
-                      float* out_gain, uint8_t* out_dl, float* out_left, hipStream_t stream);
-int tmog_hip_pair_scan(int64_t* hist, const int64_t* parent, const int64_t* parent_off, const int32_t* small_j,
-                       const int32_t* big_j, int n_pairs, const int64_t* node_hist_off, const int32_t* node_nfeat,
-                       const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B, int S,
-                       int kind, const float* node_params, int missing_bin, const int32_t* node_model,
-                       const double* qinv, int max_nfeat, void* cand_ws, int n_multi, hipStream_t stream,
-                       const int* dnp);
-int tmog_hip_zero_segments(int64_t* hist, const int64_t* off, const int64_t* size, int n, int64_t max_size,
-                           int64_t dense, int per, int S, hipStream_t stream, int n_dense, const int* dn);
-size_t tmog_hip_split_cand_bytes(int n_nodes, int max_nfeat, int B, int S);
-int tmog_hip_tree_prime();
-int tmog_hip_hist_stat_chunk(int B, int S);
-int tmog_hip_partition_fused(const uint8_t* Xb, int F, const uint32_t* rows_in, uint32_t* rows_out, const void* items,
-                             int n_items, const int64_t* node_begin, const int64_t* node_count, const int32_t* split_feat,
-                             const int32_t* split_bin, const uint8_t* dl, const float* node_params,
-                             const float* split_gain, int missing_bin, int64_t* cursors, const uint8_t* XbT, int64_t N,
-                             hipStream_t stream, const int32_t* gh_in, int32_t* gh_out, const int* dcount,
-                             int wide_rows);
-int tmog_hip_leaf_collect(const uint32_t* rows, const void* items, int n_items, uint32_t* out_rows,
-                          int32_t* out_gid, hipStream_t stream, const uint32_t* rows_alt, const int* dcount);
-}
+#include "hip/tmog_hip_abi.h"
 
 namespace {
 
@@ -104,7 +64,7 @@ std::mutex& rccl_mutex() {
 }
 
 std::vector<GpuSlot>& slots() {
-  static std::vector<GpuSlot> s(32);   // models/tree_engine.py N_SLOTS (lanes of SLOT_LANE)
+  static std::vector<GpuSlot> s(TMOG_N_SLOTS);   // handed out in lanes of TMOG_SLOT_LANE (models/tree_engine.py)
   return s;
 }
 

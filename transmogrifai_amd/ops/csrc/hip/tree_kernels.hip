@@ -21,22 +21,16 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "hip/tmog_hip_abi.h"
+
 #define TM_MAX_S 16          // narrow split scan / staged-record path: S <= 16 statistics
 #define TM_WIDE_MAX_S 256    // wide path (many classes): statistic-chunked histograms, LDS split scan
 #define TM_WIDE_MAX_BS 16384 // wide split scan keeps one feature's B x S int64 histogram in LDS
 
 namespace {
 
-struct HistItem {
-  int32_t node;     // node slot
-  int32_t fg0;      // first local feature of this group
-  int32_t nf;       // features in this group (<= 64)
-  int32_t excl;     // bit 0: this item alone covers node rows for its features (plain stores)
-                    // bit 1: every feature of the group has one present bin (register accumulation)
-  int64_t begin;    // first row entry
-  int64_t count;    // row entries in this chunk
-};
-
+// (Histogram work items: HistItem, common/tmog_abi.h.)
+//
 // Fixed-point statistics. Every per-row contribution is quantised to an integer,
 //   q = rint(v * qscale[model][s]),  |q| <= qmax = (2^31 - 1) / chunk_rows - 1,
 // with power-of-two scales chosen on the device from the per-model max |v| (tree_engine._quant_scales).
@@ -1596,15 +1590,7 @@ __global__ void fp_merge_kernel(const uint8_t* __restrict__ recv, int R, int m, 
 }
 
 // ----------------------------------------------------------------------------------- partition
-struct PartItem {
-  int32_t node;
-  int32_t pad;
-  int64_t begin;      // absolute position of the chunk in rows_in
-  int64_t count;
-  int64_t out_left;   // absolute output position for this chunk's first left row
-  int64_t out_right;  // absolute output position for this chunk's first right row
-};
-
+// (work items: PartItem, common/tmog_abi.h)
 constexpr int PART_U = 4;
 
 __device__ __forceinline__ bool goes_left(uint8_t bin, int sb, bool dl, int missing_bin) {
@@ -1701,14 +1687,7 @@ __global__ void __launch_bounds__(256) partition_fused_kernel(
 // When a node stops splitting, its row entries (still contiguous in the level's row buffer) are
 // copied out with the node id: after the last level every training entry sits in exactly one
 // (entry, leaf) pair, so boosting updates its margins by a gather instead of re-walking the tree.
-struct LeafItem {
-  int64_t begin;    // first entry in rows
-  int64_t count;
-  int64_t out;      // output position
-  int32_t gid;      // node id
-  int32_t buf;      // row buffer: 0 = rows, 1 = rows_alt (device-planned levels collect from both)
-};
-
+// (Work items: LeafItem, common/tmog_abi.h.)
 __global__ void __launch_bounds__(256) leaf_collect_kernel(const uint32_t* __restrict__ rows,
                                                            const uint32_t* __restrict__ rows_alt,
                                                            const LeafItem* __restrict__ items,
@@ -1818,7 +1797,7 @@ __global__ void __launch_bounds__(PRED_ROWS * PRED_TPR) forest_predict_lds_kerne
 constexpr int PM_ROWS = 64;
 constexpr int PM_TPR = 4;
 constexpr int PM_TU = 4;
-constexpr int PM_VK = 32;      // variants x classes accumulated per thread
+constexpr int PM_VK = TMOG_PM_VK;      // variants x classes accumulated per thread
 
 template <int KT>     // classes (compile-time: the per-thread accumulators stay in registers)
 __global__ void __launch_bounds__(PM_ROWS * PM_TPR) forest_predict_multi_kernel(

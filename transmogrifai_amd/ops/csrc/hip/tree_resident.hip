@@ -29,46 +29,7 @@
 
 #include "common/tree_grow.hpp"
 #include "hip/dev_alloc.hpp"
-
-extern "C" {
-int tmog_hip_hist_build(const uint8_t* Xb, int F, const uint32_t* rows, const void* items, int n_items,
-                        const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* node_model,
-                        const int64_t* node_hist_off, int64_t* hist, int B, int mode, int S, const float* y,
-                        const float* t1, const float* t2, int64_t stride, const float* qscale, int skip_bin,
-                        const int64_t* csr_ptr, const uint16_t* csr_col, int Sc, int n_wide, int need_general,
-                        hipStream_t stream, const int32_t* gh, const int* dcount, int wide_rows,
-                        const uint8_t* Xh, int Fh);
-int tmog_hip_split_find(const int64_t* hist, int n_nodes, const int64_t* node_hist_off, const int32_t* node_nfeat,
-                        const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B,
-                        int S, int kind, const float* node_params, int missing_bin, const int32_t* node_model,
-                        const double* qinv, int max_nfeat, void* cand_ws, int32_t* out_feat, int32_t* out_bin,
-                        float* out_gain, uint8_t* out_dl, float* out_left, float* out_total, int64_t* cursors, int n_multi,
-                        void* rec, int64_t rec_bytes, int fp_mlo, int fp_nml, int fp_obase, hipStream_t stream,
-                        unsigned* done, const int* dm);
-int tmog_hip_pair_scan(int64_t* hist, const int64_t* parent, const int64_t* parent_off, const int32_t* small_j,
-                       const int32_t* big_j, int n_pairs, const int64_t* node_hist_off, const int32_t* node_nfeat,
-                       const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B, int S,
-                       int kind, const float* node_params, int missing_bin, const int32_t* node_model,
-                       const double* qinv, int max_nfeat, void* cand_ws, int n_multi, hipStream_t stream,
-                       const int* dnp);
-int tmog_hip_zero_segments(int64_t* hist, const int64_t* off, const int64_t* size, int n, int64_t max_size,
-                           int64_t dense, int per, int S, hipStream_t stream, int n_dense, const int* dn);
-size_t tmog_hip_split_cand_bytes(int n_nodes, int max_nfeat, int B, int S);
-int tmog_hip_tree_prime();
-int tmog_hip_hist_stat_chunk(int B, int S);
-int tmog_hip_partition_fused(const uint8_t* Xb, int F, const uint32_t* rows_in, uint32_t* rows_out, const void* items,
-                             int n_items, const int64_t* node_begin, const int64_t* node_count, const int32_t* split_feat,
-                             const int32_t* split_bin, const uint8_t* dl, const float* node_params,
-                             const float* split_gain, int missing_bin, int64_t* cursors, const uint8_t* XbT, int64_t N,
-                             hipStream_t stream, const int32_t* gh_in, int32_t* gh_out, const int* dcount,
-                             int wide_rows);
-int tmog_hip_leaf_collect(const uint32_t* rows, const void* items, int n_items, uint32_t* out_rows,
-                          int32_t* out_gid, hipStream_t stream, const uint32_t* rows_alt, const int* dcount);
-int tmog_hip_fp_allgather(const void* send, void* recv, int64_t bytes, void* comm, int world, hipStream_t stream);
-int tmog_hip_fp_merge_dev(const void* recv, int R, int m_stride, int64_t rec_bytes, int S, int32_t* out_feat,
-                          int32_t* out_bin, float* out_gain, uint8_t* out_dl, float* out_left, const int* dm,
-                          hipStream_t stream);
-}
+#include "hip/tmog_hip_abi.h"
 
 // plan / finalisation arithmetic with the host twins' IEEE operation sequence (no FMA contraction)
 #pragma clang fp contract(off)
@@ -94,7 +55,7 @@ enum : int {
   C_COUNT = 16
 };
 
-constexpr int kRecFixed = 7;   // record words before the S totals: tree feat bin dl gain left right
+constexpr int kRecFixed = TMOG_REC_FIXED;   // record words before the S totals: tree feat bin dl gain left right
 
 struct PlanArgs {
   int d, T, S, chunk_rows, n_groups, n_sc, newton, subtract, pair_fuse, F_use, has_missing;
@@ -274,7 +235,7 @@ __device__ void emit_leaves(const PlanArgs& A, const PlanScratch& Z, int lvl, in
     it.count = min((int64_t)A.chunk_rows, cnt_[i] - o);
     it.out = lbase + Z.sd[i] + o;
     it.gid = A.lv_gid[lvl][i];
-    it.pad = buf;
+    it.buf = buf;
     A.litems[nl0 + k] = it;
   }
   __syncthreads();
@@ -410,7 +371,7 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
       it.count = min((int64_t)A.chunk_rows, pcnt[i] - o);
       it.out = lbase + Z.sd[i] + o;
       it.gid = A.lv_gid[P][i];
-      it.pad = P;
+      it.buf = P;
       A.litems[nl0 + k] = it;
     }
     // (c) splits -> records + children (level d), in split order
@@ -897,16 +858,6 @@ std::string unsupported(const tmog::GrowArgs& a) {
 }  // namespace
 
 extern "C" {
-
-// Outputs of one device-planned tree (models/tree_engine.py _ResidentIO).
-struct ResidentIO {
-  int64_t* rec;          // [1 + cap_nodes][7 + S] int64: header (nodes, leaf entries, error bits), then node records
-  float* gid_value;      // [cap_nodes] leaf output per created node id (pruning applied)
-  int64_t* gid_tree;     // [cap_nodes] job of each created node
-  int64_t cap_nodes;
-  const double* job_eta;    // [T]
-  const double* job_gamma;  // [T]
-};
 
 int64_t tmog_hip_resident_cap_nodes(const tmog::GrowArgs* args) {
   const tmog::GrowArgs& a = *args;

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hip/tmog_hip_abi.h"
+
 namespace {
 
 constexpr int TR = 64;   // rows per tile

@@ -6,6 +6,8 @@
 #include <cstring>
 #include <omp.h>
 
+#include "common/tmog_abi.h"
+
 static inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
 static inline uint32_t mix_k1(uint32_t k1) {

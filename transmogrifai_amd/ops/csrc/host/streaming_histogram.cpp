@@ -11,6 +11,8 @@
 #include <iterator>
 #include <map>
 
+#include "common/tmog_abi.h"
+
 namespace {
 
 struct Hist {

@@ -18,6 +18,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "common/tmog_abi.h"
+
 namespace {
 
 inline bool is_punct(uint8_t c) {

@@ -23,6 +23,8 @@
 #include <unordered_set>
 #include <vector>
 
+#include "common/tmog_abi.h"
+
 namespace {
 
 #include "unicode_tables.inc"

@@ -26,6 +26,8 @@
 #include <algorithm>
 #include <omp.h>
 
+#include "common/tmog_abi.h"
+
 constexpr int kMaxS = 256;   // statistics per bin (classes); the HIP wide path has the same bound
 
 extern "C" {

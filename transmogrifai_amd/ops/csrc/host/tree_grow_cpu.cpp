@@ -8,25 +8,8 @@
 #include <thread>
 #include <vector>
 
+#include "common/tmog_abi.h"
 #include "common/tree_grow.hpp"
-
-extern "C" {
-int tmog_hist_build_cpu(const uint8_t* Xb, int64_t N, int F, const uint32_t* rows, int n_nodes,
-                        const int64_t* node_begin, const int64_t* node_count, const int32_t* node_feat_off,
-                        const int32_t* node_nfeat, const int32_t* feat_list, const int32_t* node_model,
-                        const int64_t* node_hist_off, int64_t* hist, int B, int mode, int S, const float* y,
-                        const float* t1, const float* t2, int64_t model_stride, const float* qscale, int wide);
-int tmog_split_find_cpu(const int64_t* hist, int n_nodes, const int64_t* node_hist_off, const int32_t* node_nfeat,
-                        const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B,
-                        int S, int kind, const float* node_params, int missing_bin, const int32_t* node_model,
-                        const double* qinv, int32_t* out_feat, int32_t* out_bin, float* out_gain,
-                        uint8_t* out_default_left, float* out_left, float* out_total, uint8_t* rec,
-                        int64_t rec_bytes, int fp_mlo, int fp_nml, int fp_obase);
-int tmog_partition_cpu(const uint8_t* Xb, int F, const uint32_t* rows_in, uint32_t* rows_out, int n_nodes,
-                       const int64_t* node_begin, const int64_t* node_count, const int32_t* split_feat,
-                       const int32_t* split_bin, const uint8_t* default_left, int missing_bin,
-                       const int64_t* out_begin, int64_t* out_left_count, int wide);
-}
 
 namespace {
 
@@ -173,5 +156,10 @@ void tmog_grow_copy_cpu(void* h, int g, int64_t* tree, int64_t* feat, int64_t* b
   tmog::result_copy((tmog::GrowResult*)h, g, tree, feat, bin, dl, gain, tot, left, right);
 }
 void tmog_grow_free_cpu(void* h) { delete (tmog::GrowResult*)h; }
+
+int64_t tmog_abi_sizeof(int which) {
+  const int64_t sizes[] = {sizeof(GrowArgs), sizeof(ResidentIO), sizeof(HistItem), sizeof(PartItem), sizeof(LeafItem)};
+  return which >= 0 && which < 5 ? sizes[which] : -1;
+}
 
 }  // extern "C"

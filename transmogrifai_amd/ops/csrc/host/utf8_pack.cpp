@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "common/tmog_abi.h"
+
 namespace {
 
 template <typename CH>
