@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "common/tmog_abi.h"
+#include "common/tree_rules.hpp"
 
 namespace tmog {
 
@@ -93,49 +94,10 @@ inline int fp_delay_ms(int rank, int group) {
 
 using ::GrowArgs;   // common/tmog_abi.h
 
-// Feature-parallel split record, one per node and rank:
-//   gain f64 @0 | fpos i32 @8 (position in the full growth-order feature list, the tie-break) |
-//   bin i32 @12 | dl i32 @16 | col i32 @20 (Xb column) | left f32[S] @24
-inline size_t fp_rec_bytes(int S) { return (24 + 4 * (size_t)S + 7) & ~size_t(7); }
-
 // Merge of the ranks' records of node j (host twin of tree_kernels.hip fp_merge_kernel).
 inline void fp_merge_host(const uint8_t* recv, int R, int m, size_t rb, int S, int32_t* feat, int32_t* bin,
                           float* gain, uint8_t* dl, float* left) {
-  for (int j = 0; j < m; ++j) {
-    int w = -1;
-    double bg = -INFINITY;
-    int bf = 0x7fffffff, bd = 0, bb = 0;
-    for (int r = 0; r < R; ++r) {
-      const uint8_t* p = recv + ((size_t)r * m + j) * rb;
-      double g;
-      int32_t f, b, d;
-      std::memcpy(&g, p, 8);
-      std::memcpy(&f, p + 8, 4);
-      std::memcpy(&b, p + 12, 4);
-      std::memcpy(&d, p + 16, 4);
-      if (f == 0x7fffffff) continue;
-      const bool better = g != bg ? g > bg : (f != bf ? f < bf : (d != bd ? d < bd : b < bb));
-      if (w < 0 || better) {
-        w = r; bg = g; bf = f; bd = d; bb = b;
-      }
-    }
-    if (w < 0) {
-      feat[j] = -1;
-      bin[j] = -1;
-      gain[j] = -INFINITY;
-      dl[j] = 0;
-      for (int s = 0; s < S; ++s) left[(size_t)j * S + s] = 0.f;
-      continue;
-    }
-    const uint8_t* p = recv + ((size_t)w * m + j) * rb;
-    int32_t col;
-    std::memcpy(&col, p + 20, 4);
-    feat[j] = col;
-    bin[j] = bb;
-    gain[j] = (float)bg;
-    dl[j] = (uint8_t)bd;
-    std::memcpy(left + (size_t)j * S, p + 24, 4 * (size_t)S);
-  }
+  for (int j = 0; j < m; ++j) fp_merge_node(recv, R, m, j, (int64_t)rb, S, feat, bin, gain, dl, left);
 }
 
 struct GroupResult {
@@ -433,22 +395,16 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
     std::vector<int64_t> hist_nodes;
     for (int64_t i = 0; i < n; ++i) {
       const int t = (int)lv_tree[i];
-      can[i] = depth < a.job_depth[j0 + t] && lv_count[i] >= 2 &&
-               (double)lv_count[i] >= 2 * a.job_min_inst[j0 + t] - 1e-9;
-      // Newton trees: both children of a split need a hessian sum >= min_child_weight, so a node whose
-      // hessian (from its parent's split statistics, fp32) is clearly below 2 mcw has no valid split --
-      // skip its histogram / scan (the 1e-6 margin keeps every node that could split)
-      if (can[i] && newton && depth > 0 && a.job_mcw[j0 + t] > 0 &&
-          R.tot[(size_t)lv_gid[i] * S + 1] < 2.0 * a.job_mcw[j0 + t] * (1.0 - 1e-6))
-        can[i] = 0;
+      const bool gate = newton && depth > 0;   // the hessian: the node's second total, from its parent's split
+      can[i] = can_split(depth, a.job_depth[j0 + t], lv_count[i], a.job_min_inst[j0 + t], gate, a.job_mcw[j0 + t],
+                         gate ? R.tot[(size_t)lv_gid[i] * S + 1] : 0.0);
       need[i] = can[i] || depth == 0;
     }
     // a splittable node whose sibling cannot split still gets its histogram by subtraction from the
-    // parent's: build the sibling's (scan skipped, params slot 7 = 0) rather than the node's own
+    // parent's: build the sibling's (scan skipped: its may-split slot is 0) rather than the node's own
     if (a.subtract && !use_subset && prev_hist && depth > 0)
       for (int64_t q = 0; 2 * q + 1 < n; ++q)
-        if (need[2 * q] != need[2 * q + 1] && lv_count[2 * q] >= 1 && lv_count[2 * q + 1] >= 1 &&
-            (can[2 * q] ? lv_count[2 * q + 1] <= lv_count[2 * q] : lv_count[2 * q] <= lv_count[2 * q + 1]))
+        if (build_sibling(can[2 * q], need[2 * q], lv_count[2 * q], need[2 * q + 1], lv_count[2 * q + 1]))
           need[2 * q] = need[2 * q + 1] = 1;
     for (int64_t i = 0; i < n; ++i)
       if (need[i]) hist_nodes.push_back(i);
@@ -497,7 +453,7 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
       for (int64_t q = 0; 2 * q + 1 < n; ++q) {
         const int64_t li = 2 * q, ri = 2 * q + 1;
         if (!(need[li] && need[ri])) continue;
-        const bool left_big = lv_count[li] >= lv_count[ri];
+        const bool left_big = left_is_big(lv_count[li], lv_count[ri]);
         d_big.push_back(loc[left_big ? li : ri]);
         d_small.push_back(loc[left_big ? ri : li]);
         d_poff.push_back(pair_parent_off[q]);
@@ -506,7 +462,7 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
     std::vector<uint8_t> build(m, 1);
     for (int64_t b : d_big) build[b] = 0;
     // GPU: a sibling pair's subtraction and both children's split scans run as one pass (pair_scan_kernel)
-    // -- the two nodes are flagged (params slot 4) so the node-wise scan skips them; same decisions
+    // -- the two nodes are flagged (paired slot) so the node-wise scan skips them; same decisions
     const char* ps_env = std::getenv("TMOG_PAIR_SCAN");
     const bool pair_fuse = BK::kGPU && !use_subset && S <= 16 && B <= 64 && !d_big.empty() &&
                            !(ps_env && ps_env[0] == '0');
@@ -518,23 +474,24 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
       }
     std::vector<int64_t> nb(m), nc(m);
     std::vector<int32_t> nmd(m);
-    std::vector<float> params((size_t)m * 8, 0.f);
+    std::vector<float> params((size_t)m * kPrmStride, 0.f);
     for (int j = 0; j < m; ++j) {
       const int64_t i = hist_nodes[j];
       const int t = (int)lv_tree[i];
       nb[j] = lv_begin[i];
       nc[j] = lv_count[i];
       nmd[j] = a.job_model[j0 + t];
-      float* P = &params[(size_t)j * 8];
-      P[0] = (float)a.job_min_inst[j0 + t];
-      P[1] = (float)a.job_min_gain[j0 + t];
-      P[2] = (float)a.job_mcw[j0 + t];
-      P[3] = (float)a.job_lambda[j0 + t];
-      P[5] = a.missing_bin >= 0 ? 1.f : 0.f;
-      P[6] = (float)a.job_eps[j0 + t];
-      P[7] = can[i] ? 1.f : 0.f;
+      float* P = &params[(size_t)j * kPrmStride];
+      P[kPrmMinInst] = (float)a.job_min_inst[j0 + t];
+      P[kPrmMinGain] = (float)a.job_min_gain[j0 + t];
+      P[kPrmMcw] = (float)a.job_mcw[j0 + t];
+      P[kPrmLambda] = (float)a.job_lambda[j0 + t];
+      P[kPrmAllowMissing] = a.missing_bin >= 0 ? 1.f : 0.f;
+      P[kPrmEps] = (float)a.job_eps[j0 + t];
+      P[kPrmMaySplit] = can[i] ? 1.f : 0.f;
     }
-    for (size_t q = 0; q < d_sj.size(); ++q) params[(size_t)d_sj[q] * 8 + 4] = params[(size_t)d_bj[q] * 8 + 4] = 1.f;
+    for (size_t q = 0; q < d_sj.size(); ++q)
+      params[(size_t)d_sj[q] * kPrmStride + kPrmPaired] = params[(size_t)d_bj[q] * kPrmStride + kPrmPaired] = 1.f;
     // ---- work items (GPU) / built-node arrays (CPU)
     std::vector<HistItemH> hitems;
     std::vector<PartItemH> citems;
@@ -710,8 +667,8 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
     for (int j = 0; j < m; ++j) {
       const int64_t gid = lv_gid[hist_nodes[j]];
       for (int s = 0; s < S; ++s) R.tot[(size_t)gid * S + s] = (double)h_tot[(size_t)j * S + s];
-      const bool ok = params[(size_t)j * 8 + 7] > 0.5f && h_feat[j] >= 0 && h_gain[j] > params[(size_t)j * 8 + 6];
-      if (ok) sl.push_back(j);
+      const float* P = &params[(size_t)j * kPrmStride];
+      if (split_accepted(P, h_feat[j], h_gain + j)) sl.push_back(j);
     }
     {
       std::vector<uint8_t> splits(n, 0);

@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "common/tree_rules.hpp"
 #include "hip/tmog_hip_abi.h"
 
 #define TM_MAX_S 16          // narrow split scan / staged-record path: S <= 16 statistics
@@ -28,6 +29,8 @@
 #define TM_WIDE_MAX_BS 16384 // wide split scan keeps one feature's B x S int64 histogram in LDS
 
 namespace {
+
+using namespace tmog;   // common/tree_rules.hpp: the split / growth rules shared with the CPU twin
 
 // (Histogram work items: HistItem, common/tmog_abi.h.)
 //
@@ -688,9 +691,6 @@ __global__ void __launch_bounds__(256) hist_build_kernel(
 // columns, every bin) followed by bin 0 of each one-present-bin column -- the only words the split scan,
 // the split reduce and the next level's subtraction read of those columns (tree_grow.hpp orders the
 // multi-bin columns first), so ~530 of the headline table's ~730 columns move S words instead of B * S.
-__device__ __forceinline__ int64_t live_words(int64_t sz, int64_t dense, int per, int S) {
-  return (dense < 0 || sz <= dense) ? sz : dense + (sz - dense) / per * S;
-}
 // 32-bit index math (a node's histogram is < 2^31 words; int64 division is a long software sequence)
 __device__ __forceinline__ int live_word(int k, int dense, int per, int S) {
   if (dense < 0 || k < dense) return k;
@@ -738,93 +738,38 @@ __global__ void zero_segments_kernel(int64_t* __restrict__ hist, const int64_t* 
 // No FMA contraction from here on: gains are evaluated with exactly the CPU twin's IEEE operation
 // sequence, so near-tied candidates resolve identically on both paths (hipcc contracts by default).
 #pragma clang fp contract(off)
-__device__ __forceinline__ double impurity_dev(const double* st, int S, int kind, double* cnt) {
-  if (kind == 0 || kind == 1) {
-    double n = 0;
-    for (int s = 0; s < S; ++s) n += st[s];
-    *cnt = n;
-    if (n <= 0) return 0.0;
-    double imp = kind == 0 ? 1.0 : 0.0;
-    for (int s = 0; s < S; ++s) {
-      const double p = st[s] / n;
-      if (kind == 0) imp -= p * p;
-      else if (p > 0) imp -= p * log2(p);
-    }
-    return imp;
-  }
-  if (kind == 2) {
-    const double n = st[0];
-    *cnt = n;
-    if (n <= 0) return 0.0;
-    const double m = st[1] / n;
-    return st[2] / n - m * m;
-  }
-  *cnt = st[1];
-  return 0.0;
-}
-
 // Loops over the statistics of a node inside the SM-templated scans: unrolled to the compile-time bound with a
 // runtime guard, so the per-statistic arrays (totals, scales, left / right sums) stay in registers -- a loop to
 // the runtime S indexes them dynamically and puts them in scratch memory
 #define TM_FOR_S(s) _Pragma("unroll") for (int s = 0; s < SM; ++s) if (s < S)
 
-// impurity_dev over a register array of at most SM statistics (same operation order)
-template <int SM>
-__device__ __forceinline__ double impurity_reg(const double* st, int S, int kind, double* cnt) {
-  if (kind == 0 || kind == 1) {
-    double n = 0;
-    TM_FOR_S(s) n += st[s];
-    *cnt = n;
-    if (n <= 0) return 0.0;
-    double imp = kind == 0 ? 1.0 : 0.0;
-    TM_FOR_S(s) {
-      const double p = st[s] / n;
-      if (kind == 0) imp -= p * p;
-      else if (p > 0) imp -= p * log2(p);
-    }
-    return imp;
-  }
-  if (kind == 2) {
-    const double n = st[0];
-    *cnt = n;
-    if (n <= 0) return 0.0;
-    const double m = st[1] / n;
-    return st[2] / n - m * m;
-  }
-  *cnt = st[1];
-  return 0.0;
-}
-
-struct Best {
-  double gain;
-  int f;    // local feature index (tie-break)
-  int b;
-  int dl;
-};
-static_assert(sizeof(Best) == 24, "candidate record: three 8-byte words (store_best_sc1 / load_best_sc1)");
-
 // A candidate as three 8-byte agent-scope (sc1) words -- stores that bypass the XCD-local caching and
 // loads served from L2, for the hand-off between workgroups of the fused split reduction
-__device__ __forceinline__ void store_best_sc1(Best* p, const Best& b) {
+__device__ __forceinline__ void store_best_sc1(SplitCand* p, const SplitCand& b) {
   uint64_t* w = reinterpret_cast<uint64_t*>(p);
   __hip_atomic_store(w, (uint64_t)__double_as_longlong(b.gain), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(w + 1, (uint64_t)(uint32_t)b.f | ((uint64_t)(uint32_t)b.b << 32), __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(w + 2, (uint64_t)(uint32_t)b.dl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ Best load_best_sc1(const Best* p) {
+__device__ __forceinline__ SplitCand load_best_sc1(const SplitCand* p) {
   const uint64_t* w = reinterpret_cast<const uint64_t*>(p);
   const uint64_t g = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint64_t fb = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint64_t dl = __hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return Best{__longlong_as_double((long long)g), (int)(uint32_t)fb, (int)(uint32_t)(fb >> 32), (int)(uint32_t)dl};
+  return SplitCand{__longlong_as_double((long long)g), (int)(uint32_t)fb, (int)(uint32_t)(fb >> 32), (int)(uint32_t)dl};
 }
 
-__device__ __forceinline__ bool better(const Best& a, const Best& b) {
-  if (a.gain != b.gain) return a.gain > b.gain;
-  if (a.f != b.f) return a.f < b.f;
-  if (a.dl != b.dl) return a.dl < b.dl;
-  return a.b < b.b;
+// the wave's best candidate, on every lane
+__device__ __forceinline__ void wave_best(SplitCand& best) {
+  for (int off = 32; off > 0; off >>= 1) {
+    SplitCand o;
+    o.gain = __shfl_xor(best.gain, off, 64);
+    o.f = __shfl_xor(best.f, off, 64);
+    o.b = __shfl_xor(best.b, off, 64);
+    o.dl = __shfl_xor(best.dl, off, 64);
+    if (better(o, best)) best = o;
+  }
 }
 
 // Split scan, two kernels. split_scan_kernel: grid (node, feature block of FPB = 16 features); each
@@ -871,7 +816,7 @@ struct ReduceArgs {
   const double* qinv;
   int fbmax;
   int cstride;      // candidate slots per node (fbmax rounded up to 16: 384 B, whole 128-B lines per node)
-  const Best* cand;
+  const SplitCand* cand;
   int32_t* out_feat;
   int32_t* out_bin;
   float* out_gain;
@@ -889,21 +834,14 @@ struct ReduceArgs {
 __device__ __forceinline__ void reduce_node(const ReduceArgs& ra, int j, int lane, bool sc1 = false) {
   const int B = ra.B, S = ra.S, fbmax = ra.fbmax, missing_bin = ra.missing_bin;
   if (ra.cursors && lane < 2) ra.cursors[2 * j + lane] = 0;   // partition_fused_kernel's per-node slot cursors
-  Best b{-INFINITY, 0x7fffffff, 0, 0};
+  SplitCand b = SplitCand::none();
   for (int i = lane; i < fbmax; i += 64) {      // any number of feature blocks
-    const Best* cp = ra.cand + (int64_t)j * ra.cstride + i;
-    const Best c = sc1 ? load_best_sc1(cp) : *cp;
+    const SplitCand* cp = ra.cand + (int64_t)j * ra.cstride + i;
+    const SplitCand c = sc1 ? load_best_sc1(cp) : *cp;
     if (better(c, b)) b = c;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o;
-    o.gain = __shfl_xor(b.gain, off, 64);
-    o.f = __shfl_xor(b.f, off, 64);
-    o.b = __shfl_xor(b.b, off, 64);
-    o.dl = __shfl_xor(b.dl, off, 64);
-    if (better(o, b)) b = o;
-  }
-  const bool found = b.f != 0x7fffffff && b.gain > -INFINITY;
+  wave_best(b);
+  const bool found = b.found() && b.gain > -INFINITY;
   const int64_t* h = ra.hist + ra.node_hist_off[j];
   const double* qi = ra.qinv + (int64_t)(ra.node_model ? ra.node_model[j] : 0) * S;
   if (lane == 0) {
@@ -927,17 +865,14 @@ __device__ __forceinline__ void reduce_node(const ReduceArgs& ra, int j, int lan
     if (lane == 0) {
       ra.out_total[(int64_t)j * S + s] = (float)((double)t * qi[s]);
       ra.out_left[(int64_t)j * S + s] = (float)((double)l * qi[s]);
-      if (ra.rec) reinterpret_cast<float*>(ra.rec + (int64_t)j * ra.rec_bytes + 24)[s] = (float)((double)l * qi[s]);
+      if (ra.rec)
+        reinterpret_cast<float*>(ra.rec + (int64_t)j * ra.rec_bytes + kFpLeft)[s] = (float)((double)l * qi[s]);
     }
   }
-  if (ra.rec && lane == 0) {   // feature-parallel split record (common/tree_grow.hpp fp_rec_bytes)
+  if (ra.rec && lane == 0) {   // feature-parallel split record
     uint8_t* r = ra.rec + (int64_t)j * ra.rec_bytes;
-    *reinterpret_cast<double*>(r) = found ? b.gain : -INFINITY;
-    reinterpret_cast<int32_t*>(r)[2] =
-        found ? (b.f < ra.fp_nml ? ra.fp_mlo + b.f : ra.fp_obase + (b.f - ra.fp_nml)) : 0x7fffffff;
-    reinterpret_cast<int32_t*>(r)[3] = found ? b.b : -1;
-    reinterpret_cast<int32_t*>(r)[4] = found ? b.dl : 0;
-    reinterpret_cast<int32_t*>(r)[5] = found ? ra.feat_list[ra.node_feat_off[j] + b.f] : -1;
+    fp_rec_store(r, found, b, ra.fp_mlo, ra.fp_nml, ra.fp_obase,
+                 [&] { return ra.feat_list[ra.node_feat_off[j] + b.f]; });
   }
 }
 
@@ -953,29 +888,29 @@ struct NodeScan {
   double tcount, pimp, parent_gain, min_inst, min_gain, mcw, lambda;
   int S, kind;
   bool allow_missing;
-  Best best;
+  SplitCand best;
 
   // totq_in: the node's fixed-point totals (every lane holds the same values)
   __device__ __forceinline__ void init(const int64_t* totq_in, const double* qi, const float* P, int S_, int kind_,
                                        int missing_bin) {
     S = S_;
     kind = NEWTON ? 3 : kind_;
-    best = Best{-INFINITY, 0x7fffffff, 0, 0};
-    min_inst = P[0];
-    min_gain = P[1];
-    mcw = P[2];
-    lambda = P[3];
-    allow_missing = P[5] > 0.5f && missing_bin >= 0;
+    best = SplitCand::none();
+    min_inst = P[kPrmMinInst];
+    min_gain = P[kPrmMinGain];
+    mcw = P[kPrmMcw];
+    lambda = P[kPrmLambda];
+    allow_missing = P[kPrmAllowMissing] > 0.5f && missing_bin >= 0;
     TM_FOR_S(s) {
       totq[s] = totq_in[s];
       q[s] = qi[s];
       tot[s] = (double)totq[s] * q[s];
     }
     if constexpr (NEWTON) {
-      parent_gain = tot[0] * tot[0] / (tot[1] + lambda);
+      parent_gain = newton_parent(tot[0], tot[1], lambda);
     } else {
-      pimp = impurity_reg<SM>(tot, S, kind, &tcount);
-      parent_gain = kind == 3 ? tot[0] * tot[0] / (tot[1] + lambda) : 0.0;
+      pimp = impurity<SM>([&](int s) { return tot[s]; }, S, kind, &tcount);
+      parent_gain = kind == 3 ? newton_parent(tot[0], tot[1], lambda) : 0.0;
     }
   }
 
@@ -990,18 +925,16 @@ struct NodeScan {
     bool ok = true;
     if (NEWTON || kind == 3) {
       // invalid by min_child_weight: skip the two fp64 divisions (whole waves skip at small nodes)
-      if (left[1] < mcw || right[1] < mcw) return;
-      gain = left[0] * left[0] / (left[1] + lambda) + right[0] * right[0] / (right[1] + lambda) - parent_gain;
+      if (newton_invalid(left[1], right[1], mcw)) return;
+      gain = newton_gain(left[0], left[1], right[0], right[1], lambda, parent_gain);
     } else if constexpr (!NEWTON) {
       double lc, rc;
-      const double li = impurity_reg<SM>(left, S, kind, &lc);
-      const double ri = impurity_reg<SM>(right, S, kind, &rc);
-      if (lc < min_inst || rc < min_inst || lc <= 0 || rc <= 0) ok = false;
-      gain = pimp - (lc / tcount) * li - (rc / tcount) * ri;
-      if (gain < min_gain) ok = false;
+      const double li = impurity<SM>([&](int s) { return left[s]; }, S, kind, &lc);
+      const double ri = impurity<SM>([&](int s) { return right[s]; }, S, kind, &rc);
+      ok = impurity_split_gain(pimp, tcount, lc, li, rc, ri, min_inst, min_gain, &gain);
     }
     if (ok) {
-      Best c{gain, f, b, dl};
+      SplitCand c{gain, f, b, dl};
       if (better(c, best)) best = c;
     }
   }
@@ -1026,17 +959,6 @@ struct NodeScan {
     }
   }
 
-  // wave-level best (every lane ends with it)
-  __device__ __forceinline__ void wave_best() {
-    for (int off = 32; off > 0; off >>= 1) {
-      Best o;
-      o.gain = __shfl_xor(best.gain, off, 64);
-      o.f = __shfl_xor(best.f, off, 64);
-      o.b = __shfl_xor(best.b, off, 64);
-      o.dl = __shfl_xor(best.dl, off, 64);
-      if (better(o, best)) best = o;
-    }
-  }
 };
 
 // node totals from local feature 0 of a histogram (every row is counted once per feature, including the
@@ -1083,7 +1005,7 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
     const int32_t* __restrict__ node_feat_off, const int32_t* __restrict__ feat_list,
     const int32_t* __restrict__ feat_nbins, int B, int S, int kind, const float* __restrict__ node_params,
     int missing_bin, const int32_t* __restrict__ node_model, const double* __restrict__ qinv, int fbmax,
-    Best* __restrict__ cand, int n_multi, int fpb, unsigned* __restrict__ done, ReduceArgs ra,
+    SplitCand* __restrict__ cand, int n_multi, int fpb, unsigned* __restrict__ done, ReduceArgs ra,
     const int* __restrict__ dm) {
   const int cstride = ra.cstride;
   if constexpr (NEWTON) S = SM;      // the launcher takes this instantiation at S == SM only: no run-time S guards
@@ -1093,9 +1015,9 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
   const int lane = threadIdx.x & 63;
   // NEWTON: the wave index as a scalar, so the feature index, its bin count and row offset are too
   const int wave = NEWTON ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
-  // params slot 4: the node was scanned with its subtraction partner by pair_scan_kernel (same cand slots, all
+  // paired slot: the node was scanned with its subtraction partner by pair_scan_kernel (same cand slots, all
   // written by that earlier launch): with the fused reduction its block 0 reduces it, the others have nothing to do
-  if (node_params[(int64_t)j * 8 + 4] > 0.5f) {
+  if (node_params[(int64_t)j * kPrmStride + kPrmPaired] > 0.5f) {
     if (done && fb == 0 && wave == 0) reduce_node(ra, j, lane);
     return;
   }
@@ -1105,11 +1027,11 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
   const int f_lim = n_multi >= 0 ? min(n_multi, nf) : nf;
   const int fb_multi = n_multi >= 0 ? (n_multi + fpb - 1) / fpb : fbmax;
   const bool one_blk = fb >= fb_multi;
-  __shared__ Best s_best[4];
+  __shared__ SplitCand s_best[4];
   NodeScan<SM, NEWTON> ns;
-  ns.best = Best{-INFINITY, 0x7fffffff, 0, 0};
-  // params slot 7 = "may split" (tree_grow.hpp): nodes built only as a subtraction partner are not scanned
-  if (node_params[(int64_t)j * 8 + 7] > 0.5f &&
+  ns.best = SplitCand::none();
+  // "may split" slot (tree_grow.hpp): nodes built only as a subtraction partner are not scanned
+  if (node_params[(int64_t)j * kPrmStride + kPrmMaySplit] > 0.5f &&
       (one_blk ? (n_multi + (fb - fb_multi) * 256 < nf) : (fb * fpb < f_lim))) {
     const int64_t* h = hist + node_hist_off[j];
     const int32_t* fl = feat_list + node_feat_off[j];
@@ -1135,8 +1057,8 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
     } else {
       node_totals<SM>(h, B, S, lane, totq);
     }
-    ns.init(totq, qinv + (int64_t)(node_model ? node_model[j] : 0) * S, node_params + (int64_t)j * 8, S, kind,
-            missing_bin);
+    ns.init(totq, qinv + (int64_t)(node_model ? node_model[j] : 0) * S, node_params + (int64_t)j * kPrmStride, S,
+            kind, missing_bin);
     if (one_blk) {
       const int f = n_multi + (fb - fb_multi) * 256 + (int)threadIdx.x;
       if (f < nf && ns.allow_missing && feat_nbins[fl[f]] == 1) {
@@ -1194,12 +1116,12 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
       }
     }
   }
-  ns.wave_best();
+  wave_best(ns.best);
   if (lane == 0) s_best[wave] = ns.best;
   __syncthreads();
   if (done == nullptr) {
     if (threadIdx.x == 0) {
-      Best b = s_best[0];
+      SplitCand b = s_best[0];
       for (int w = 1; w < 4; ++w)
         if (better(s_best[w], b)) b = s_best[w];
       cand[(int64_t)j * cstride + fb] = b;
@@ -1221,7 +1143,7 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
   if (wave == 0) {
     unsigned last = 0;
     if (lane == 0) {
-      Best b = s_best[0];
+      SplitCand b = s_best[0];
       for (int w = 1; w < 4; ++w)
         if (better(s_best[w], b)) b = s_best[w];
       store_best_sc1(cand + (int64_t)j * cstride + fb, b);
@@ -1242,7 +1164,7 @@ __global__ void __launch_bounds__(256) split_scan_kernel(
 // one node: it loads the parent's and the built (small) child's rows, stores big = parent - small, and
 // scans both children from registers -- the histograms the subtraction already streams are not read
 // again by a separate scan. Node totals: small from its feature 0, big = parent's - small's. Writes
-// cand[j_small][fb] and cand[j_big][fb]; the two nodes carry params slot 4 = 1 so split_scan_kernel skips
+// cand[j_small][fb] and cand[j_big][fb]; the two nodes carry the paired slot so split_scan_kernel skips
 // them. Words outside the live set (one-present-bin columns above bin 0) are left alone, as before.
 // Load schedule. The kernel is bound by exposed load latency, not by VALU issue or bandwidth (profiles/README.md):
 // a wave runs a chain of dependent loads (pair -> node offsets -> rows) and then up to four features of ~400
@@ -1262,7 +1184,7 @@ __global__ void __launch_bounds__(256) pair_scan_kernel(
     const int32_t* __restrict__ node_feat_off, const int32_t* __restrict__ feat_list,
     const int32_t* __restrict__ feat_nbins, int B, int S, int kind, const float* __restrict__ node_params,
     int missing_bin, const int32_t* __restrict__ node_model, const double* __restrict__ qinv, int fbmax,
-    Best* __restrict__ cand, int n_multi, int fpb, int cstride, const int* __restrict__ dnp) {
+    SplitCand* __restrict__ cand, int n_multi, int fpb, int cstride, const int* __restrict__ dnp) {
   if constexpr (NEWTON) S = SM;      // the launcher takes this instantiation at S == SM only: no run-time S guards
   const int q = blockIdx.x / fbmax;
   const int fb = blockIdx.x - q * fbmax;
@@ -1280,7 +1202,8 @@ __global__ void __launch_bounds__(256) pair_scan_kernel(
   int nf = node_nfeat[js];                 // no per-node feature subsets on this path: same list for both
   int64_t hs_off = node_hist_off[js], hb_off = node_hist_off[jb];
   int fl_off = node_feat_off[js];
-  float may_s = node_params[(int64_t)js * 8 + 7], may_b = node_params[(int64_t)jb * 8 + 7];
+  float may_s = node_params[(int64_t)js * kPrmStride + kPrmMaySplit];
+  float may_b = node_params[(int64_t)jb * kPrmStride + kPrmMaySplit];
   if constexpr (NEWTON) batch_end(nf, hs_off, hb_off, fl_off, may_s, may_b);
   const int64_t* P = parent + poff;
   const int64_t* Hs = hist + hs_off;
@@ -1299,7 +1222,7 @@ __global__ void __launch_bounds__(256) pair_scan_kernel(
     load_row<SM>(P, f, B, S, lane, np_);
     nb_next = feat_nbins[fl[f]];
   };
-  __shared__ Best s_best[2][4];
+  __shared__ SplitCand s_best[2][4];
   NodeScan<SM, NEWTON> ns, nb_;
   {
     int64_t ts[SM], tp[SM], tb[SM];
@@ -1317,8 +1240,8 @@ __global__ void __launch_bounds__(256) pair_scan_kernel(
     }
     TM_FOR_S(s) tb[s] = tp[s] - ts[s];
     const int model_s = node_model ? node_model[js] : 0, model_b = node_model ? node_model[jb] : 0;
-    ns.init(ts, qinv + (int64_t)model_s * S, node_params + (int64_t)js * 8, S, kind, missing_bin);
-    nb_.init(tb, qinv + (int64_t)model_b * S, node_params + (int64_t)jb * 8, S, kind, missing_bin);
+    ns.init(ts, qinv + (int64_t)model_s * S, node_params + (int64_t)js * kPrmStride, S, kind, missing_bin);
+    nb_.init(tb, qinv + (int64_t)model_b * S, node_params + (int64_t)jb * kPrmStride, S, kind, missing_bin);
   }
   // feature f from this lane's rows pa (built child) and pp (parent): the big child's row out, both scans
   auto scan_pair = [&](int f, int nbins, const int64_t* pa, const int64_t* pp) {
@@ -1388,15 +1311,15 @@ __global__ void __launch_bounds__(256) pair_scan_kernel(
       scan_pair(f, nbins, pa, pp);
     }
   }
-  ns.wave_best();
-  nb_.wave_best();
+  wave_best(ns.best);
+  wave_best(nb_.best);
   if (lane == 0) {
     s_best[0][wave] = ns.best;
     s_best[1][wave] = nb_.best;
   }
   __syncthreads();
   if (threadIdx.x < 2) {
-    Best b = s_best[threadIdx.x][0];
+    SplitCand b = s_best[threadIdx.x][0];
     for (int w = 1; w < 4; ++w)
       if (better(s_best[threadIdx.x][w], b)) b = s_best[threadIdx.x][w];
     cand[(int64_t)(threadIdx.x ? jb : js) * cstride + fb] = b;
@@ -1413,24 +1336,24 @@ __global__ void __launch_bounds__(256) split_scan_wide_kernel(
     const int32_t* __restrict__ node_feat_off, const int32_t* __restrict__ feat_list,
     const int32_t* __restrict__ feat_nbins, int B, int S, int kind, const float* __restrict__ node_params,
     int missing_bin, const int32_t* __restrict__ node_model, const double* __restrict__ qinv, int fbmax,
-    Best* __restrict__ cand, int n_multi, int cstride) {
+    SplitCand* __restrict__ cand, int n_multi, int cstride) {
   extern __shared__ __attribute__((aligned(16))) int64_t wl[];
   int64_t* H = wl;                       // [B][S] prefix sums
   int64_t* totq = H + (int64_t)B * S;    // [S]
   int64_t* miss = totq + S;              // [S]
   double* q = reinterpret_cast<double*>(miss + S);   // [S]
-  __shared__ Best s_best[4];
+  __shared__ SplitCand s_best[4];
   const int j = blockIdx.x / fbmax;
   const int f = blockIdx.x - j * fbmax;
   const int nf = node_nfeat[j];
-  Best best{-INFINITY, 0x7fffffff, 0, 0};
-  const bool live = f < nf && node_params[(int64_t)j * 8 + 7] > 0.5f;   // slot 7: node may split
+  SplitCand best = SplitCand::none();
+  const float* P = node_params + (int64_t)j * kPrmStride;
+  const bool live = f < nf && P[kPrmMaySplit] > 0.5f;
   const int64_t* h = hist + node_hist_off[j];
   const int32_t* fl = feat_list + node_feat_off[j];
-  const float* P = node_params + (int64_t)j * 8;
   const double* qi = qinv + (int64_t)(node_model ? node_model[j] : 0) * S;
-  const double min_inst = P[0], min_gain = P[1], mcw = P[2], lambda = P[3];
-  const bool allow_missing = P[5] > 0.5f && missing_bin >= 0;
+  const double min_inst = P[kPrmMinInst], min_gain = P[kPrmMinGain], mcw = P[kPrmMcw], lambda = P[kPrmLambda];
+  const bool allow_missing = P[kPrmAllowMissing] > 0.5f && missing_bin >= 0;
   const int nb = live ? feat_nbins[fl[f]] : 0;
   const bool one = live && n_multi >= 0 && f >= n_multi;     // one-present-bin column: bin 0 only
   const int64_t* hf = h + (int64_t)f * B * S;
@@ -1450,24 +1373,11 @@ __global__ void __launch_bounds__(256) split_scan_wide_kernel(
       for (int bb = 1; bb < B; ++bb) H[(int64_t)bb * S + s] += H[(int64_t)(bb - 1) * S + s];
   __syncthreads();
   if (live) {
-    // parent impurity with the CPU twin's arithmetic
-    double tcount = 0, pimp = 0, parent_gain = 0;
-    if (kind == 0 || kind == 1) {
-      for (int s = 0; s < S; ++s) tcount += (double)totq[s] * q[s];
-      if (tcount > 0) {
-        pimp = kind == 0 ? 1.0 : 0.0;
-        for (int s = 0; s < S; ++s) {
-          const double p = ((double)totq[s] * q[s]) / tcount;
-          if (kind == 0) pimp -= p * p;
-          else if (p > 0) pimp -= p * log2(p);
-        }
-      }
-    } else {
-      double tot[4] = {0, 0, 0, 0};
-      for (int s = 0; s < S && s < 4; ++s) tot[s] = (double)totq[s] * q[s];
-      pimp = impurity_dev(tot, S, kind, &tcount);
-      parent_gain = kind == 3 ? tot[0] * tot[0] / (tot[1] + lambda) : 0.0;
-    }
+    // the CPU twin's arithmetic over the scaled LDS sums (the integer expressions in its operation order)
+    auto tot = [&](int s) { return (double)totq[s] * q[s]; };
+    double tcount = 0;
+    const double pimp = impurity<0>(tot, S, kind, &tcount);
+    const double parent_gain = kind == 3 ? newton_parent(tot(0), tot(1), lambda) : 0.0;
     const int nd = allow_missing ? 2 : 1;
     const int nbc = one ? 1 : nb - 1 + (allow_missing ? 1 : 0);   // candidate bins per direction
     for (int c = threadIdx.x; c < nbc * nd; c += blockDim.x) {
@@ -1475,73 +1385,31 @@ __global__ void __launch_bounds__(256) split_scan_wide_kernel(
       if (one && (dl || !allow_missing)) continue;
       if (!one && b == nb - 1 && dl) continue;
       const int64_t* lp = H + (int64_t)b * S;
+      auto left = [&](int s) { return (double)(lp[s] + (dl ? miss[s] : 0)) * q[s]; };
+      auto right = [&](int s) { return (double)(totq[s] - lp[s] - (dl ? miss[s] : 0)) * q[s]; };
       double gain;
-      bool ok = true;
-      if (kind == 0 || kind == 1) {
-        double lc = 0, rc = 0;
-        for (int s = 0; s < S; ++s) {
-          const int64_t lq = lp[s] + (dl ? miss[s] : 0);
-          lc += (double)lq * q[s];
-          rc += (double)(totq[s] - lq) * q[s];
-        }
-        double li = 0, ri = 0;
-        if (lc > 0) {
-          li = kind == 0 ? 1.0 : 0.0;
-          for (int s = 0; s < S; ++s) {
-            const double p = ((double)(lp[s] + (dl ? miss[s] : 0)) * q[s]) / lc;
-            if (kind == 0) li -= p * p;
-            else if (p > 0) li -= p * log2(p);
-          }
-        }
-        if (rc > 0) {
-          ri = kind == 0 ? 1.0 : 0.0;
-          for (int s = 0; s < S; ++s) {
-            const double p = ((double)(totq[s] - lp[s] - (dl ? miss[s] : 0)) * q[s]) / rc;
-            if (kind == 0) ri -= p * p;
-            else if (p > 0) ri -= p * log2(p);
-          }
-        }
-        if (lc < min_inst || rc < min_inst || lc <= 0 || rc <= 0) ok = false;
-        gain = pimp - (lc / tcount) * li - (rc / tcount) * ri;
-        if (gain < min_gain) ok = false;
+      bool ok;
+      if (kind == 3) {
+        ok = !newton_invalid(left(1), right(1), mcw);
+        gain = newton_gain(left(0), left(1), right(0), right(1), lambda, parent_gain);
       } else {
-        double left[4] = {0, 0, 0, 0}, right[4] = {0, 0, 0, 0};
-        for (int s = 0; s < S && s < 4; ++s) {
-          const int64_t lq = lp[s] + (dl ? miss[s] : 0);
-          left[s] = (double)lq * q[s];
-          right[s] = (double)(totq[s] - lq) * q[s];
-        }
-        if (kind == 3) {
-          if (left[1] < mcw || right[1] < mcw) ok = false;
-          gain = left[0] * left[0] / (left[1] + lambda) + right[0] * right[0] / (right[1] + lambda) - parent_gain;
-        } else {
-          double lc, rc;
-          const double li = impurity_dev(left, S, kind, &lc);
-          const double ri = impurity_dev(right, S, kind, &rc);
-          if (lc < min_inst || rc < min_inst || lc <= 0 || rc <= 0) ok = false;
-          gain = pimp - (lc / tcount) * li - (rc / tcount) * ri;
-          if (gain < min_gain) ok = false;
-        }
+        double lc, rc;
+        const double li = impurity<0>(left, S, kind, &lc);
+        const double ri = impurity<0>(right, S, kind, &rc);
+        ok = impurity_split_gain(pimp, tcount, lc, li, rc, ri, min_inst, min_gain, &gain);
       }
       if (ok) {
-        const Best cb{gain, f, b, dl};
+        const SplitCand cb{gain, f, b, dl};
         if (better(cb, best)) best = cb;
       }
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o;
-    o.gain = __shfl_xor(best.gain, off, 64);
-    o.f = __shfl_xor(best.f, off, 64);
-    o.b = __shfl_xor(best.b, off, 64);
-    o.dl = __shfl_xor(best.dl, off, 64);
-    if (better(o, best)) best = o;
-  }
+  wave_best(best);
   if (lane == 0) s_best[wave] = best;
   __syncthreads();
   if (threadIdx.x == 0) {
-    Best bb = s_best[0];
+    SplitCand bb = s_best[0];
     for (int w = 1; w < 4; ++w)
       if (better(s_best[w], bb)) bb = s_best[w];
     cand[(int64_t)j * cstride + f] = bb;
@@ -1552,7 +1420,7 @@ __global__ void __launch_bounds__(64) split_reduce_kernel(ReduceArgs ra) { reduc
 
 // Feature-parallel merge: node j's decision is the best of the R ranks' records under the split scan's
 // order (gain, then lowest full-list position, dl, bin) -- the candidate a single rank scanning every
-// feature would pick. Host twin: common/tree_grow.hpp fp_merge_host.
+// feature would pick (fp_merge_node, shared with common/tree_grow.hpp fp_merge_host).
 // m_stride: records per rank in recv (the all-gather's count; >= m); dm (device-planned levels): the real node count
 // is read from device memory, the grid covers the host bound m.
 __global__ void fp_merge_kernel(const uint8_t* __restrict__ recv, int R, int m, int64_t rb, int S,
@@ -1561,41 +1429,12 @@ __global__ void fp_merge_kernel(const uint8_t* __restrict__ recv, int R, int m, 
                                 float* __restrict__ out_left, int64_t m_stride, const int* __restrict__ dm) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m || (dm != nullptr && j >= *dm)) return;
-  int w = -1;
-  Best best{-INFINITY, 0x7fffffff, 0, 0};
-  for (int r = 0; r < R; ++r) {
-    const uint8_t* p = recv + ((int64_t)r * m_stride + j) * rb;
-    const int32_t* pi = reinterpret_cast<const int32_t*>(p);
-    const Best c{*reinterpret_cast<const double*>(p), pi[2], pi[3], pi[4]};
-    if (c.f == 0x7fffffff) continue;
-    if (w < 0 || better(c, best)) {
-      w = r;
-      best = c;
-    }
-  }
-  if (w < 0) {
-    out_feat[j] = -1;
-    out_bin[j] = -1;
-    out_gain[j] = -INFINITY;
-    out_dl[j] = 0;
-    for (int s = 0; s < S; ++s) out_left[(int64_t)j * S + s] = 0.f;
-    return;
-  }
-  const uint8_t* p = recv + ((int64_t)w * m_stride + j) * rb;
-  out_feat[j] = reinterpret_cast<const int32_t*>(p)[5];
-  out_bin[j] = best.b;
-  out_gain[j] = (float)best.gain;
-  out_dl[j] = (uint8_t)best.dl;
-  for (int s = 0; s < S; ++s) out_left[(int64_t)j * S + s] = reinterpret_cast<const float*>(p + 24)[s];
+  fp_merge_node(recv, R, m_stride, j, rb, S, out_feat, out_bin, out_gain, out_dl, out_left);
 }
 
 // ----------------------------------------------------------------------------------- partition
 // (work items: PartItem, common/tmog_abi.h)
 constexpr int PART_U = 4;
-
-__device__ __forceinline__ bool goes_left(uint8_t bin, int sb, bool dl, int missing_bin) {
-  return (missing_bin >= 0 && bin == missing_bin) ? dl : ((int)bin <= sb);
-}
 
 // One-pass partition (replaces count + scatter): every chunk of every node reads its split decision
 // straight from split_find's device output (no host round trip before the partition), and each
@@ -1616,7 +1455,8 @@ __global__ void __launch_bounds__(256) partition_fused_kernel(
   const int j = it.node;
   const int f = split_feat[j], sb = split_bin[j];
   // the host's split decision, evaluated identically: splittable node, a split found, gain above eps
-  if (f < 0 || !(node_params[(int64_t)j * 8 + 7] > 0.5f) || !(split_gain[j] > node_params[(int64_t)j * 8 + 6])) return;
+  const float* P = node_params + (int64_t)j * kPrmStride;
+  if (!split_accepted(P, f, split_gain + j)) return;
   const bool d = dl[j] != 0;
   const int64_t nb = node_begin[j], nend = nb + node_count[j];
   // PART_U rows per thread per pass: their row / bin loads are all in flight together and one pair
@@ -1644,7 +1484,7 @@ __global__ void __launch_bounds__(256) partition_fused_kernel(
     int wpre[PART_U];
 #pragma unroll
     for (int u = 0; u < PART_U; ++u) {
-      lf[u] = vd[u] && goes_left(bn[u], sb, d, missing_bin);
+      lf[u] = vd[u] && goes_left(bn[u], sb, [&] { return d; }, missing_bin);
       const unsigned long long m = __ballot(lf[u]);
       wpre[u] = __popcll(m & below);
       if (lane == 0) s_cnt[u][wave] = __popcll(m);
@@ -1756,7 +1596,7 @@ __global__ void __launch_bounds__(PRED_ROWS * PRED_TPR) forest_predict_lds_kerne
         for (int u = 0; u < PRED_TU; ++u) {
           if (nd[u].z >= 0) {
             const uint8_t b = xr[nd[u].x];
-            const bool gl = (missing_bin >= 0 && b == missing_bin) ? (default_left[k[u]] != 0) : ((int)b <= nd[u].y);
+            const bool gl = goes_left(b, nd[u].y, [&] { return default_left[k[u]] != 0; }, missing_bin);
             k[u] = gl ? nd[u].z : nd[u].w;
             nd[u] = nodes[k[u]];
             active = true;
@@ -1869,7 +1709,7 @@ __global__ void __launch_bounds__(PM_ROWS * PM_TPR) forest_predict_multi_kernel(
             }
             if (live[u] != 0u) {
               const uint8_t b = xr[nd[u].x];
-              const bool gl = (missing_bin >= 0 && b == missing_bin) ? (default_left[k[u]] != 0) : ((int)b <= nd[u].y);
+              const bool gl = goes_left(b, nd[u].y, [&] { return default_left[k[u]] != 0; }, missing_bin);
               k[u] = gl ? nd[u].z : nd[u].w;
               nd[u] = nodes[k[u]];
               dep[u] += 1;
@@ -1925,7 +1765,7 @@ __global__ void __launch_bounds__(256) forest_predict_kernel(
       for (int u = 0; u < 4; ++u) {
         if (nd[u].z >= 0) {
           const uint8_t b = xr[nd[u].x];
-          const bool gl = (missing_bin >= 0 && b == missing_bin) ? (default_left[k[u]] != 0) : ((int)b <= nd[u].y);
+          const bool gl = goes_left(b, nd[u].y, [&] { return default_left[k[u]] != 0; }, missing_bin);
           k[u] = gl ? nd[u].z : nd[u].w;
           nd[u] = nodes[k[u]];
           active = true;
@@ -1943,7 +1783,7 @@ __global__ void __launch_bounds__(256) forest_predict_kernel(
     int4 nd = nodes[k];  // (feat, bin, left, right)
     while (nd.z >= 0) {
       const uint8_t b = xr[nd.x];
-      const bool gl = (missing_bin >= 0 && b == missing_bin) ? (default_left[k] != 0) : ((int)b <= nd.y);
+      const bool gl = goes_left(b, nd.y, [&] { return default_left[k] != 0; }, missing_bin);
       k = gl ? nd.z : nd.w;
       nd = nodes[k];
     }
@@ -2030,18 +1870,14 @@ int tmog_hip_hist_build(const uint8_t* Xb, int F, const uint32_t* rows, const vo
   return (int)hipGetLastError();
 }
 
-// live words of the largest node: the grids of the subtract / zero kernels are sized to what they touch
+// The grids of the subtract / zero kernels are sized to the live words of the largest node, what they touch
 // (sized from the full B x S words they launched ~4x the workgroups the live region needs)
-static int64_t host_live_words(int64_t sz, int64_t dense, int per, int S) {
-  return (dense < 0 || sz <= dense) ? sz : dense + (sz - dense) / per * S;
-}
-
 int tmog_hip_hist_subtract(int64_t* hist, const int64_t* parent, const int64_t* parent_off, const int64_t* small_off,
                            const int64_t* out_off, const int64_t* size, int n, int64_t max_size, int64_t dense,
                            int per, int S, hipStream_t stream) {
   if (n == 0) return 0;
   if (max_size >= (int64_t)1 << 31) return -2;
-  int gx = (int)min((host_live_words(max_size, dense, per, S) + 255) / 256, (int64_t)1024);
+  int gx = (int)min((live_words(max_size, dense, per, S) + 255) / 256, (int64_t)1024);
   if (gx < 1) gx = 1;
   hipLaunchKernelGGL(hist_subtract_kernel, dim3(gx, n), dim3(256), 0, stream, hist, parent, parent_off, small_off,
                      out_off, size, n, dense, per, S);
@@ -2059,7 +1895,7 @@ int tmog_hip_split_find(const int64_t* hist, int n_nodes, const int64_t* node_hi
   // device-counted launches take the narrow scan with the fused reduction (no separate per-node launch)
   if (dm != nullptr && (done == nullptr || S > TM_MAX_S || B > 64)) return -2;
   if (n_multi > max_nfeat) n_multi = -1;
-  Best* cand = (Best*)cand_ws;   // >= tmog_hip_split_cand_bytes(n_nodes, max_nfeat, B, S) bytes
+  SplitCand* cand = (SplitCand*)cand_ws;   // >= tmog_hip_split_cand_bytes(n_nodes, max_nfeat, B, S) bytes
   const bool wide = S > TM_MAX_S || B > 64;
   int fbmax;
   // done (n_nodes zeroed counters, left zeroed): the node reduction runs inside the narrow scan's last block
@@ -2100,7 +1936,7 @@ int tmog_hip_split_find(const int64_t* hist, int n_nodes, const int64_t* node_hi
 }
 
 // Fused subtraction + split scan of sibling pairs (pair_scan_kernel); the same candidate layout as
-// tmog_hip_split_find, whose scan then skips the pairs' nodes (params slot 4). Narrow path only.
+// tmog_hip_split_find, whose scan then skips the pairs' nodes (the paired slot). Narrow path only.
 int tmog_hip_pair_scan(int64_t* hist, const int64_t* parent, const int64_t* parent_off, const int32_t* small_j,
                        const int32_t* big_j, int n_pairs, const int64_t* node_hist_off, const int32_t* node_nfeat,
                        const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B, int S,
@@ -2116,7 +1952,7 @@ int tmog_hip_pair_scan(int64_t* hist, const int64_t* parent, const int64_t* pare
 #define TM_PAIR(...)                                                                                           \
   hipLaunchKernelGGL((pair_scan_kernel<__VA_ARGS__>), dim3(n_pairs * fbmax), dim3(256), 0, stream, hist, parent, parent_off, \
                      small_j, big_j, n_pairs, node_hist_off, node_nfeat, node_feat_off, feat_list, feat_nbins, B, S, \
-                     kind, node_params, missing_bin, node_model, qinv, fbmax, (Best*)cand_ws, n_multi, fpb,    \
+                     kind, node_params, missing_bin, node_model, qinv, fbmax, (SplitCand*)cand_ws, n_multi, fpb,    \
                      cand_stride(fbmax), dnp)
   if (scan_newton(kind, S)) TM_PAIR(2, true);
   else if (S <= 2) TM_PAIR(2, false);
@@ -2150,7 +1986,7 @@ int tmog_hip_zero_segments(int64_t* hist, const int64_t* off, const int64_t* siz
                            int64_t dense, int per, int S, hipStream_t stream, int n_dense, const int* dn) {
   if (n == 0) return 0;
   if (max_size >= (int64_t)1 << 31) return -2;
-  const int64_t lw = std::max(host_live_words(max_size, dense, per, S), host_live_words(max_size, 0, per, S));
+  const int64_t lw = std::max(live_words(max_size, dense, per, S), live_words(max_size, 0, per, S));
   int gx = (int)min((lw + 255) / 256, (int64_t)1024);
   if (gx < 1) gx = 1;
   hipLaunchKernelGGL(zero_segments_kernel, dim3(gx, n), dim3(256), 0, stream, hist, off, size, n, dense, per, S,
@@ -2170,7 +2006,7 @@ int tmog_hip_tree_prime() {
 size_t tmog_hip_split_cand_bytes(int n_nodes, int max_nfeat, int B, int S) {
   const bool wide = S > TM_MAX_S || B > 64;
   const int fpb = split_fpb();       // (max_nfeat + fpb - 1) / fpb + 1 bounds fbmax for any n_multi split
-  return (size_t)n_nodes * cand_stride(wide ? max_nfeat : (max_nfeat + fpb - 1) / fpb + 1) * sizeof(Best);
+  return (size_t)n_nodes * cand_stride(wide ? max_nfeat : (max_nfeat + fpb - 1) / fpb + 1) * sizeof(SplitCand);
 }
 
 // Largest statistic chunk whose per-workgroup LDS table (64 copies of B x Sc words) fits the LDS.

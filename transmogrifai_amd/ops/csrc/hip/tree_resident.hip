@@ -333,8 +333,8 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
       if (j >= 0) {
         int64_t* r = R(A.lv_gid[P][i]);
         for (int s = 0; s < S; ++s) r[kRecFixed + s] = dbits((double)A.r_tot[(int64_t)j * S + s]);
-        const float* Pp = A.par[P] + (int64_t)j * 8;
-        split = Pp[7] > 0.5f && A.r_feat[j] >= 0 && A.r_gain[j] > Pp[6];
+        const float* Pp = A.par[P] + (int64_t)j * tmog::kPrmStride;
+        split = tmog::split_accepted(Pp, A.r_feat[j], A.r_gain + j);
       }
       const int64_t c = pcnt[i];
       const bool leaf = !split && c > 0;
@@ -438,12 +438,9 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
   const bool dense_split = A.live_dense >= 0 && A.live_dense < A.hsz;
   auto can_split = [&](int i) {
     const int jt = ltree[i];
-    const int64_t c = lcnt[i];
-    bool can = d < A.j_depth[jt] && c >= 2 && (double)c >= 2 * A.j_inst[jt] - 1e-9;
-    if (can && A.newton && d > 0 && A.j_mcw[jt] > 0 &&
-        bitsd(R(A.lv_gid[C][i])[kRecFixed + 1]) < 2.0 * A.j_mcw[jt] * (1.0 - 1e-6))
-      can = false;
-    return can;
+    const bool gate = A.newton && d > 0;       // the hessian: the node's second total, recorded by its parent's split
+    return tmog::can_split(d, A.j_depth[jt], lcnt[i], A.j_inst[jt], gate, A.j_mcw[jt],
+                           gate ? bitsd(R(A.lv_gid[C][i])[kRecFixed + 1]) : 0.0);
   };
   auto counts = [&](int i, int fl) {
     const bool need = fl & 2;
@@ -480,10 +477,9 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
       bool nl = cl, nr = cr;
       // subtraction pairing: when one sibling needs a histogram, the other gets one too if it is the smaller
       // (built) one -- then the bigger one is derived from the parent
-      if (nl != nr && lcnt[li] >= 1 && lcnt[ri] >= 1 && (cl ? lcnt[ri] <= lcnt[li] : lcnt[li] <= lcnt[ri]))
-        nl = nr = true;
+      if (tmog::build_sibling(cl, nl, lcnt[li], nr, lcnt[ri])) nl = nr = true;
       const bool pair = nl && nr;
-      const bool left_big = lcnt[li] >= lcnt[ri];
+      const bool left_big = tmog::left_is_big(lcnt[li], lcnt[ri]);
       counts(li, (cl ? 1 : 0) | (nl ? 2 : 0) | (pair ? 4 : 0) | (pair && left_big ? 8 : 0));
       counts(ri, (cr ? 1 : 0) | (nr ? 2 : 0) | (pair && !left_big ? 8 : 0));
     }
@@ -532,15 +528,15 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
     A.nfo[j] = 0;
     A.nnf[j] = A.F_use;
     const bool paired = d > 0 && (((i & 1) == 0 && (fl & 4)) || ((i & 1) == 1 && (Z.flag[i - 1] & 4)));
-    float* Pp = A.par[C] + (int64_t)j * 8;
-    Pp[0] = (float)A.j_inst[jt];
-    Pp[1] = (float)A.j_gain[jt];
-    Pp[2] = (float)A.j_mcw[jt];
-    Pp[3] = (float)A.j_lam[jt];
-    Pp[4] = paired ? 1.f : 0.f;             // pair_fuse: the pair scan derives / scans both siblings
-    Pp[5] = A.has_missing ? 1.f : 0.f;
-    Pp[6] = (float)A.j_eps[jt];
-    Pp[7] = (fl & 1) ? 1.f : 0.f;
+    float* Pp = A.par[C] + (int64_t)j * tmog::kPrmStride;
+    Pp[tmog::kPrmMinInst] = (float)A.j_inst[jt];
+    Pp[tmog::kPrmMinGain] = (float)A.j_gain[jt];
+    Pp[tmog::kPrmMcw] = (float)A.j_mcw[jt];
+    Pp[tmog::kPrmLambda] = (float)A.j_lam[jt];
+    Pp[tmog::kPrmPaired] = paired ? 1.f : 0.f;             // pair_fuse: the pair scan derives / scans both siblings
+    Pp[tmog::kPrmAllowMissing] = A.has_missing ? 1.f : 0.f;
+    Pp[tmog::kPrmEps] = (float)A.j_eps[jt];
+    Pp[tmog::kPrmMaySplit] = (fl & 1) ? 1.f : 0.f;
     if (fl & 4) {                          // left node of a pair: (small, big) histogram nodes, parent offset
       const int jr = (int)Z.sa[i + 1];
       const bool left_big = fl & 8;
@@ -662,10 +658,7 @@ __global__ void __launch_bounds__(1024) tree_finalize_kernel(FinArgs A) {
       const int64_t jt = r[0];
       const double t0 = bitsd(r[kRecFixed]);
       const double t1 = A.S > 1 ? bitsd(r[kRecFixed + 1]) : 0.0;
-      double v;
-      if (A.mode == 1) v = t0 > 0 ? t1 / fmax(t0, 1e-300) : 0.0;
-      else v = -t0 / (t1 + A.j_lam[jt]) * A.j_eta[jt];
-      A.gid_value[i] = (float)v;
+      A.gid_value[i] = (float)tmog::leaf_value(A.mode, t0, t1, A.j_lam[jt], A.j_eta[jt]);
       A.gid_tree[i] = jt;
     }
     if (t == 0) {
@@ -680,10 +673,7 @@ __global__ void __launch_bounds__(1024) tree_finalize_kernel(FinArgs A) {
     const int64_t jt = r[0];
     const double t0 = bitsd(r[kRecFixed]);
     const double t1 = A.S > 1 ? bitsd(r[kRecFixed + 1]) : 0.0;
-    double v;
-    if (A.mode == 1) v = t0 > 0 ? t1 / fmax(t0, 1e-300) : 0.0;
-    else v = -t0 / (t1 + A.j_lam[jt]) * A.j_eta[jt];
-    A.value[i] = v;
+    A.value[i] = tmog::leaf_value(A.mode, t0, t1, A.j_lam[jt], A.j_eta[jt]);
     A.left_w[i] = r[5];
     A.right_w[i] = r[6];
     A.parent[i] = -1;

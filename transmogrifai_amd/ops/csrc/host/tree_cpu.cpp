@@ -27,6 +27,9 @@
 #include <omp.h>
 
 #include "common/tmog_abi.h"
+#include "common/tree_rules.hpp"
+
+using namespace tmog;   // the split / growth rules shared with the HIP twins
 
 constexpr int kMaxS = 256;   // statistics per bin (classes); the HIP wide path has the same bound
 
@@ -87,34 +90,7 @@ int tmog_hist_build_cpu(const uint8_t* Xb, int64_t N, int F, const uint32_t* row
 }
 
 // ---------------------------------------------------------------------------------- split finding
-// Impurity kinds: 0 gini, 1 entropy, 2 variance, 3 newton (xgboost gain).
-static inline double impurity(const double* st, int S, int kind, double* count_out) {
-  if (kind == 0 || kind == 1) {
-    double n = 0;
-    for (int s = 0; s < S; ++s) n += st[s];
-    *count_out = n;
-    if (n <= 0) return 0.0;
-    double imp = kind == 0 ? 1.0 : 0.0;
-    for (int s = 0; s < S; ++s) {
-      const double p = st[s] / n;
-      if (kind == 0) imp -= p * p;
-      else if (p > 0) imp -= p * std::log2(p);
-    }
-    return imp;
-  }
-  if (kind == 2) {
-    const double n = st[0];
-    *count_out = n;
-    if (n <= 0) return 0.0;
-    const double m = st[1] / n;
-    return st[2] / n - m * m;
-  }
-  *count_out = st[1];
-  return 0.0;
-}
-
-// params per node (float): [0] min_instances, [1] min_info_gain, [2] min_child_weight, [3] lambda,
-// [4] alpha (unused), [5] allow_missing (xgb default-direction search)
+// (impurity kinds, gains and the node parameter slots: common/tree_rules.hpp)
 int tmog_split_find_cpu(const int64_t* hist, int n_nodes, const int64_t* node_hist_off, const int32_t* node_nfeat,
                         const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B,
                         int S, int kind, const float* node_params, int missing_bin, const int32_t* node_model,
@@ -126,10 +102,10 @@ int tmog_split_find_cpu(const int64_t* hist, int n_nodes, const int64_t* node_hi
     const int64_t* h = hist + node_hist_off[j];
     const int nf = node_nfeat[j];
     const int32_t* fl = feat_list + node_feat_off[j];
-    const float* P = node_params + (int64_t)j * 8;
+    const float* P = node_params + (int64_t)j * kPrmStride;
     const double* q = qinv + (int64_t)(node_model ? node_model[j] : 0) * S;
-    const double min_inst = P[0], min_gain = P[1], mcw = P[2], lambda = P[3];
-    const bool allow_missing = P[5] > 0.5f && missing_bin >= 0;
+    const double min_inst = P[kPrmMinInst], min_gain = P[kPrmMinGain], mcw = P[kPrmMcw], lambda = P[kPrmLambda];
+    const bool allow_missing = P[kPrmAllowMissing] > 0.5f && missing_bin >= 0;
     int64_t totq[kMaxS] = {0};
     double tot[kMaxS];
     // totals from feature 0 (every row is counted once per feature, including the missing bin)
@@ -140,8 +116,8 @@ int tmog_split_find_cpu(const int64_t* hist, int n_nodes, const int64_t* node_hi
       out_total[(int64_t)j * S + s] = (float)tot[s];
     }
     double tcount;
-    const double pimp = impurity(tot, S, kind, &tcount);
-    const double parent_gain = kind == 3 ? tot[0] * tot[0] / (tot[1] + lambda) : 0.0;
+    const double pimp = impurity<0>([&](int s) { return tot[s]; }, S, kind, &tcount);
+    const double parent_gain = kind == 3 ? newton_parent(tot[0], tot[1], lambda) : 0.0;
     double best = -INFINITY;
     int bf = -1, bb = -1, bdl = 0, bfi = -1;
     int64_t bleft[kMaxS] = {0};
@@ -170,17 +146,15 @@ int tmog_split_find_cpu(const int64_t* hist, int n_nodes, const int64_t* node_hi
           }
           double gain;
           if (kind == 3) {
-            if (left[1] < mcw || right[1] < mcw) continue;
-            gain = left[0] * left[0] / (left[1] + lambda) + right[0] * right[0] / (right[1] + lambda) - parent_gain;
+            if (newton_invalid(left[1], right[1], mcw)) continue;
+            gain = newton_gain(left[0], left[1], right[0], right[1], lambda, parent_gain);
           } else {
             double lc, rc;
-            const double li = impurity(left, S, kind, &lc);
-            const double ri = impurity(right, S, kind, &rc);
-            if (lc < min_inst || rc < min_inst || lc <= 0 || rc <= 0) continue;
-            gain = pimp - (lc / tcount) * li - (rc / tcount) * ri;
-            if (gain < min_gain) continue;
+            const double li = impurity<0>([&](int s) { return left[s]; }, S, kind, &lc);
+            const double ri = impurity<0>([&](int s) { return right[s]; }, S, kind, &rc);
+            if (!impurity_split_gain(pimp, tcount, lc, li, rc, ri, min_inst, min_gain, &gain)) continue;
           }
-          if (gain > best) {
+          if (gain > best) {   // first wins: the (feature, dl, bin) scan order is better()'s tie-break
             best = gain; bf = gf; bb = b; bdl = dl; bfi = f;
             for (int s = 0; s < S; ++s) bleft[s] = lq[s];
           }
@@ -192,14 +166,10 @@ int tmog_split_find_cpu(const int64_t* hist, int n_nodes, const int64_t* node_hi
     out_gain[j] = bf >= 0 ? (float)best : -INFINITY;
     out_default_left[j] = (uint8_t)bdl;
     for (int s = 0; s < S; ++s) out_left[(int64_t)j * S + s] = (float)((double)bleft[s] * q[s]);
-    if (rec) {   // feature-parallel split record (common/tree_grow.hpp fp_rec_bytes)
+    if (rec) {   // feature-parallel split record
       uint8_t* r = rec + (int64_t)j * rec_bytes;
-      const double g = bf >= 0 ? best : -INFINITY;
-      const int32_t fpos = bf >= 0 ? (bfi < fp_nml ? fp_mlo + bfi : fp_obase + (bfi - fp_nml)) : 0x7fffffff;
-      const int32_t vals[4] = {fpos, bb, bdl, bf};
-      std::memcpy(r, &g, 8);
-      std::memcpy(r + 8, vals, 16);
-      std::memcpy(r + 24, out_left + (int64_t)j * S, 4 * (size_t)S);
+      fp_rec_store(r, bf >= 0, SplitCand{best, bfi, bb, bdl}, fp_mlo, fp_nml, fp_obase, [&] { return bf; });
+      std::memcpy(r + kFpLeft, out_left + (int64_t)j * S, 4 * (size_t)S);
     }
   }
   return 0;
@@ -216,21 +186,19 @@ int tmog_partition_cpu(const uint8_t* Xb, int F, const uint32_t* rows_in, uint32
   for (int j = 0; j < n_nodes; ++j) {
     if (split_feat[j] < 0) { out_left_count[j] = 0; continue; }
     const int f = split_feat[j], sb = split_bin[j];
-    const bool dl = default_left[j] != 0;
+    const auto dl = [&] { return default_left[j] != 0; };
     const uint32_t* in = rows_in + node_begin[j];
     const int64_t cnt = node_count[j];
     int64_t nl = 0;
     for (int64_t i = 0; i < cnt; ++i) {
       const int bin = Xb[(int64_t)(wide ? in[i] : (in[i] & 0xFFFFFFu)) * F + f];
-      const bool left = (missing_bin >= 0 && bin == missing_bin) ? dl : (bin <= sb);
-      nl += left;
+      nl += goes_left(bin, sb, dl, missing_bin);
     }
     uint32_t* out = rows_out + out_begin[j];
     int64_t li = 0, ri = nl;
     for (int64_t i = 0; i < cnt; ++i) {
       const int bin = Xb[(int64_t)(wide ? in[i] : (in[i] & 0xFFFFFFu)) * F + f];
-      const bool left = (missing_bin >= 0 && bin == missing_bin) ? dl : (bin <= sb);
-      if (left) out[li++] = in[i]; else out[ri++] = in[i];
+      if (goes_left(bin, sb, dl, missing_bin)) out[li++] = in[i]; else out[ri++] = in[i];
     }
     out_left_count[j] = nl;
   }
@@ -257,8 +225,8 @@ int tmog_forest_predict_cpu(const uint8_t* Xb, int F, int n_models, const int64_
       for (int64_t t = model_tree_off[m]; t < model_tree_off[m + 1]; ++t) {
         int64_t k = tree_off[t];
         while (nodes[4 * k + 2] >= 0) {
-          const int b = xr[nodes[4 * k]];
-          const bool gl = (missing_bin >= 0 && b == missing_bin) ? (default_left[k] != 0) : (b <= nodes[4 * k + 1]);
+          const auto dl = [&] { return default_left[k] != 0; };
+          const bool gl = goes_left(xr[nodes[4 * k]], nodes[4 * k + 1], dl, missing_bin);
           k = gl ? nodes[4 * k + 2] : nodes[4 * k + 3];
         }
         const float w = tree_weight[t];
@@ -414,14 +382,15 @@ extern "C" int64_t tmog_tree_finalize_cpu(int64_t n, int T, const int64_t* tree,
     if (mode == 0) {
       double s = 0;
       for (int c = 0; c < S; ++c) s += t[c];
-      for (int c = 0; c < K; ++c) value[(size_t)i * K + c] = s > 0 ? t[c] / std::max(s, 1e-300) : 0.0;
+      // a class frequency t[c] / s is leaf_value's guarded mean (mode 1) of (s, t[c]); lambda and eta are not read
+      for (int c = 0; c < K; ++c) value[(size_t)i * K + c] = leaf_value(1, s, t[c], 0.0, 0.0);
       cover[i] = s;
     } else if (mode == 1) {
-      value[i] = t[0] > 0 ? t[1] / std::max(t[0], 1e-300) : 0.0;
+      value[i] = leaf_value(mode, t[0], t[1], 0.0, 0.0);
       cover[i] = t[0];
     } else {
       const int64_t j = tree[i];
-      value[i] = -t[0] / (t[1] + job_lam[j]) * job_eta[j];
+      value[i] = leaf_value(mode, t[0], t[1], job_lam[j], job_eta[j]);
       cover[i] = t[1];
     }
   }
