@@ -12,10 +12,17 @@ import pytest
 import torch
 
 import tree_level_oracle as O
+from transmogrifai_amd.ops._native import ABI_CONSTS
 
 SENT, SENT32 = O.SENT, O.SENT32
 COUNTS = [1, 63, 64, 65, 255, 256, 257, 1025, 4096]          # rows per item (chunk_rows = 4096)
-X_ONE, X_REG, X_CSR, X_LIVE0, X_WIDE = 1, 2, 4, 8, 16         # HistItem.excl bits
+# HistItem.excl bits and the statistic-chunk shift, as common/tmog_abi.h names them
+X_ONE, X_REG, X_CSR, X_LIVE0, X_WIDE, X_SC = (ABI_CONSTS["TMOG_ITEM_" + k]
+                                              for k in ("SOLE", "REG", "CSR", "LIVE0", "WIDE", "SC_SHIFT"))
+
+
+def test_item_flags_keep_their_values():
+    assert (X_ONE, X_REG, X_CSR, X_LIVE0, X_WIDE, X_SC) == (1, 2, 4, 8, 16, 8)
 
 
 def _lib():
@@ -121,7 +128,7 @@ def _expect(L, items, *, Sc=0, gh=None, dcount=None, zero=None):
         if x & (X_CSR | X_LIVE0):
             idx, H = idx[:, 0, :], H[:, 0, :]
         elif Sc:
-            s0 = ((x >> 8) & 0xFF) * Sc
+            s0 = ((x >> X_SC) & 0xFF) * Sc
             idx, H = idx[:, :, s0:s0 + Sc], H[:, :, s0:s0 + Sc]
         if x & X_ONE:
             buf[idx] = H
@@ -136,7 +143,7 @@ def _node_zero(L, nodes, dense=-1):
 
 def _std_items(L, f0, nf, excl=0, single=None, multi=None, step=1025):
     """One single-chunk item (excl bit 0) per node of ``single``; ``multi`` nodes are cut into ``step``-row chunks
-    that accumulate atomically (bit 0 clear: "h.excl = (nit == 1 ? 1 : 0) | ...", grow_group)."""
+    that accumulate atomically (bit 0 clear: "nit == 1 ? TMOG_ITEM_SOLE : 0", hist_item_at in common/tree_plan.hpp)."""
     rows = []
     for j in single:
         rows.append((j, f0, nf, excl | X_ONE, L["node_begin"][j], L["node_count"][j]))
@@ -171,8 +178,8 @@ def test_hist_byte_gather(mode, S, nf):
 @pytest.mark.parametrize("S", [3, 40, 256])
 def test_hist_stat_chunks(S):
     """Mode 0 with B = 256: B x S does not fit the LDS table, so each statistic chunk [c * Sc, c * Sc + Sc) is its
-    own item (chunk index in excl bits 8..15, "| (sc << 8)" in grow_group) writing disjoint words; the last chunk
-    of S = 3 is narrower than Sc. Every class occurs, so the first and last slot of every chunk is hit."""
+    own item (chunk index from excl bit TMOG_ITEM_SC_SHIFT up, hist_item_at in common/tree_plan.hpp) writing disjoint
+    words; the last chunk of S = 3 is narrower than Sc. Every class occurs, so the first and last slot of every chunk is hit."""
     lib = _lib()
     B, nf = 256, 5
     Sc = lib.tmog_hip_hist_stat_chunk(B, S)
@@ -185,8 +192,8 @@ def test_hist_stat_chunks(S):
     L["rows"][:700] = O.pack(np.arange(700), rng.choice([1, 2, 255], 700))
     rows = []
     for sc in range(n_sc):
-        rows.append((0, 1, nf, X_ONE | (sc << 8), 0, 700))
-        rows += [(1, 1, nf, sc << 8, b, c) for b, c in _chunks(700, 650, 300)]
+        rows.append((0, 1, nf, X_ONE | (sc << X_SC), 0, 700))
+        rows += [(1, 1, nf, sc << X_SC, b, c) for b, c in _chunks(700, 650, 300)]
     items = _items(rows)
     zero = _node_zero(L, [1])
     got = _build(L, items, Sc=Sc, zero=zero)
@@ -224,9 +231,10 @@ def test_hist_sparse_missing_bin_byte_path():
 @pytest.mark.parametrize("live0", [0, 1])
 @pytest.mark.parametrize("nf", [7, 64])
 def test_hist_register_path(nf, live0):
-    """excl bit 1 ("FeatGroup{n_multi + g.f0, g.nf, GPU, false}": one-present-bin columns, sparse mode only): bins
-    in {0, skip_bin}. With excl bit 3 ("(fgp.reg || fgp.csr) && live_dense >= 0 ? 8 : 0") only the first S words
-    -- bin 0 -- of each feature are written; without it (no multi-bin column, live_dense = -1) all B x S."""
+    """excl bit 1 ("FeatGroup{n_multi + g.f0, g.nf, GPU ? TMOG_ITEM_REG : 0}": one-present-bin columns, sparse mode
+    only): bins in {0, skip_bin}. With excl bit 3 ("(reg || csr) && live_dense >= 0 ? TMOG_ITEM_LIVE0 : 0") only the
+    first S words -- bin 0 -- of each feature are written; without it (no multi-bin column, live_dense = -1) all
+    B x S."""
     rng = np.random.default_rng(nf + live0)
     B, n_multi = 8, 2
     counts = [1, 64, 65, 1025, 4096, 1025 + 1025 + 77]

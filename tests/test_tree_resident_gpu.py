@@ -8,7 +8,9 @@ import torch
 from transmogrifai_amd.models import tree_engine as te
 
 
-def _problem(dev, F=136, n_one=12, N=20_000, n_jobs=3, depth=7, B=32, seed=11, gamma=0.1, mcw=0.5):
+def _problem(dev, F=136, n_one=12, N=20_000, n_jobs=3, depth=7, B=32, seed=11, gamma=0.1, mcw=0.5, rows=None):
+    """``rows(m, N)``: the training rows of job m (default: all but every (m + 2)-th)."""
+    rows = rows or (lambda m, N: torch.arange(N)[torch.arange(N) % (m + 2) != 1])
     g = torch.Generator().manual_seed(seed)
     X = torch.randint(0, B - 1, (N, F), generator=g, dtype=torch.uint8)
     X[torch.rand(N, F, generator=g) < 0.1] = B - 1
@@ -20,7 +22,7 @@ def _problem(dev, F=136, n_one=12, N=20_000, n_jobs=3, depth=7, B=32, seed=11, g
     t2 = torch.rand(n_jobs, N, generator=g) * 0.25 + 0.01
     jobs = [te.TreeJob(m, te.TreeParams(max_depth=depth - (m % 2), min_child_weight=mcw * (1 + m), reg_lambda=1.0,
                                         gamma=gamma * m, eta=0.3, split_eps=1e-6),
-                       torch.arange(N)[torch.arange(N) % (m + 2) != 1].to(dev)) for m in range(n_jobs)]
+                       rows(m, N).to(dev)) for m in range(n_jobs)]
     Xd = X.to(dev)
     return dict(Xb=Xd, n_bins=nbins, jobs=jobs, t1=t1.to(dev), t2=t2.to(dev), B=B, missing_bin=B - 1,
                 csr=te.onebin_csr(Xd, nbins) if n_one else None)
@@ -43,13 +45,18 @@ def _per_row(la, n_rows):
     return key[o], gid[o], val[o]
 
 
+CASES = [(136, 12, 4096, 7, 0.1, {}), (68, 0, 1024, 5, 0.1, {}), (200, 24, 512, 9, 0.1, {}), (66, 10, 4096, 6, 0.1, {}),
+         (136, 12, 4096, 8, 0.0, {}),
+         # the item boundaries: a root of exactly 8 row chunks = 4 partition / CSR items, and one of 1024 rows + 1
+         (68, 8, 512, 4, 0.1, dict(N=4096, n_jobs=2, rows=lambda m, N: torch.arange(N if m == 0 else 1025)))]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("F,n_one,chunk,depth,gamma", [(136, 12, 4096, 7, 0.1), (68, 0, 1024, 5, 0.1),
-                                                       (200, 24, 512, 9, 0.1), (66, 10, 4096, 6, 0.1),
-                                                       (136, 12, 4096, 8, 0.0)])
-def test_resident_trees_match_host_planned(F, n_one, chunk, depth, gamma):
+@pytest.mark.parametrize("F,n_one,chunk,depth,gamma,sized", CASES,
+                         ids=["-".join(map(str, c[:5])) + ("-boundaries" if c[5] else "") for c in CASES])
+def test_resident_trees_match_host_planned(F, n_one, chunk, depth, gamma, sized):
     """gamma 0: the finalisation's no-pruning fast path; gamma > 0: level-wise pruning."""
-    pb = _problem("cuda", F=F, n_one=n_one, depth=depth, gamma=gamma)
+    pb = _problem("cuda", F=F, n_one=n_one, depth=depth, gamma=gamma, **sized)
     host = _grow(pb, False, chunk)
     res = _grow(pb, True, chunk)
     assert isinstance(res, te.ResidentTree), "device-planned path not taken"

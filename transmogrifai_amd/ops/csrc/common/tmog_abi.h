@@ -22,16 +22,26 @@
 #define TMOG_PART_ITEM_ROWS 1024   // rows per partition item (GPU)
 #define TMOG_PM_VK 32              // forest_predict_multi_kernel: variants x classes accumulated per thread
 
-// ---- work items of the tree level kernels (hip/tree_kernels.hip), planned by common/tree_grow.hpp on the host
-// and by hip/tree_resident.hip on the device
+// ---- flags of a histogram item (HistItem.excl); REG, CSR and WIDE are also the flags of a feature group
+#define TMOG_ITEM_SOLE 1           // this item alone covers the node's rows for its features (plain stores)
+#define TMOG_ITEM_REG 2            // every feature of the group has one present bin (register accumulation)
+#define TMOG_ITEM_CSR 4            // CSR item: walks the rows' lists of one-present-bin columns
+#define TMOG_ITEM_LIVE0 8          // only the bin-0 words of each feature are written out
+#define TMOG_ITEM_WIDE 16          // wide-load item: contiguous dword-aligned physical columns
+#define TMOG_ITEM_SC_SHIFT 8       // bits 8..15: statistic chunk
+
+// ---- work items of the tree level kernels (hip/tree_kernels.hip), laid out by common/tree_plan.hpp for the host
+// planner (common/tree_grow.hpp) and the device planner (hip/tree_resident.hip)
+typedef struct FeatGroup {
+  int32_t f0, nf;   // local features [f0, f0 + nf) of one histogram item (nf <= 64)
+  int32_t flags;    // TMOG_ITEM_REG | TMOG_ITEM_CSR | TMOG_ITEM_WIDE
+} FeatGroup;
+
 typedef struct HistItem {
   int32_t node;     // node slot
   int32_t fg0;      // first local feature of this group
   int32_t nf;       // features in this group (<= 64)
-  int32_t excl;     // bit 0: this item alone covers node rows for its features (plain stores)
-                    // bit 1: every feature of the group has one present bin (register accumulation)
-                    // bit 2: CSR item, bit 3: only the bin-0 words of each feature are written out,
-                    // bit 4: wide-load item, bits 8..15: statistic chunk
+  int32_t excl;     // TMOG_ITEM_* flags | statistic chunk << TMOG_ITEM_SC_SHIFT
   int64_t begin;    // first row entry
   int64_t count;    // row entries in this chunk
 } HistItem;
@@ -54,6 +64,17 @@ typedef struct LeafItem {
 } LeafItem;
 
 static_assert(sizeof(HistItem) == 32 && sizeof(PartItem) == 40 && sizeof(LeafItem) == 32, "item layout");
+static_assert(sizeof(FeatGroup) == 12, "group layout");
+
+// A level's items. Nodes that need a histogram take node slots in node order. Each gets partition items of
+// TMOG_PART_ITEM_ROWS rows (one item when it has fewer, an empty node included). A built node (needed, not derived
+// from its parent and sibling) gets histogram items: per feature group, per statistic chunk, per row chunk, of
+// TMOG_CSR_ITEM_ROWS rows for the CSR group and chunk_rows for every other; only groups without REG / CSR take one
+// item per statistic chunk; SOLE marks the only row chunk, LIVE0 the REG / CSR groups when the one-present-bin
+// columns' live words are bin 0 only (live_dense >= 0). The list holds the WIDE items of every node first, then the
+// others. A node split over row chunks accumulates atomically and is zeroed first: the whole node when any chunk_rows
+// group has several chunks (or no dense prefix is known), else the region past live_dense when only the CSR group
+// has. Leaf items cut a node's rows into chunk_rows slices (none for an empty node), written one node after the other.
 
 // ---- arguments of one grower call (tmog_grow_forest_cpu / tmog_hip_grow_forest / tmog_hip_grow_resident)
 typedef struct GrowArgs {
@@ -214,6 +235,16 @@ int64_t tmog_grow_leaf_count_cpu(void* h, int g);
 void tmog_grow_copy_cpu(void* h, int g, int64_t* tree, int64_t* feat, int64_t* bin, uint8_t* dl, double* gain,
                         double* tot, int64_t* left, int64_t* right);
 void tmog_grow_free_cpu(void* h);
+// The work items of one level as both planners lay them out (a loop over common/tree_plan.hpp, for tests). Node i has
+// count[i] rows from begin[i] and the planners' flag bits flags[i] (1 can split, 2 needs a histogram, 4 left node of
+// a pair, 8 the pair's derived node); every node without bit 2 is collected as a leaf (gid i, buffer 0, output from 0).
+// Histogram nodes take slots in node order, slot j at word j * hsz. totals[7] receives the numbers of histogram,
+// partition and leaf items, of zero segments, of whole-node zero segments (listed first), of wide-load items and
+// whether any item takes the byte-gather path. Null output arrays: only the totals are written.
+void tmog_level_items_cpu(int n, const int64_t* count, const int64_t* begin, const int32_t* flags,
+                          const FeatGroup* groups, int n_groups, int64_t chunk_rows, int n_sc, int64_t live_dense,
+                          int64_t hsz, HistItem* hitems, PartItem* citems, LeafItem* litems, int64_t* z_off,
+                          int64_t* z_size, int64_t* totals);
 
 #ifdef __cplusplus
 }  // extern "C"

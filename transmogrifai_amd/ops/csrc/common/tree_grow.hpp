@@ -12,7 +12,8 @@
 // Backends (template parameter BK) provide memory, staging and the kernels:
 //   GPU  (hip/tree_grow_hip.hip)   : pinned staging + hipMemcpyAsync, tmog_hip_* launchers
 //   CPU  (host/tree_grow_cpu.cpp)  : host memory, tmog_*_cpu functions (bit-identical results)
-// Layout contracts are those of hip/tree_kernels.hip (packed rows, int64 fixed-point histograms).
+// Layout contracts are those of hip/tree_kernels.hip (packed rows, int64 fixed-point histograms); how a level's nodes
+// become work items is common/tree_plan.hpp, shared with the device planner (hip/tree_resident.hip).
 #pragma once
 
 #include <algorithm>
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "common/tmog_abi.h"
+#include "common/tree_plan.hpp"
 #include "common/tree_rules.hpp"
 
 namespace tmog {
@@ -169,23 +171,13 @@ struct FpSlice {
   int32_t mlo, nml, obase;   // local feature f -> position f < nml ? mlo + f : obase + (f - nml)
 };
 
-struct FeatGroup {
-  int f0, nf;
-  bool reg;
-  bool csr = false;
-  bool wide = false;   // GPU: contiguous dword-aligned physical columns -> wide-load histogram items
-};
-
-constexpr int64_t kCsrRows = TMOG_CSR_ITEM_ROWS;    // rows per CSR histogram item (GPU)
-constexpr int64_t kPartRows = TMOG_PART_ITEM_ROWS;  // rows per partition item (GPU)
-
 // n features in near-equal groups of at most 64
 inline std::vector<FeatGroup> equal_groups(int n) {
   std::vector<FeatGroup> out;
   if (n <= 0) return out;
   const int ng = std::max(1, (n + 63) / 64);
   const int fg = (n + ng - 1) / ng;
-  for (int gi = 0; gi * fg < n; ++gi) out.push_back(FeatGroup{gi * fg, std::min(fg, n - gi * fg), false, false});
+  for (int gi = 0; gi * fg < n; ++gi) out.push_back(FeatGroup{gi * fg, std::min(fg, n - gi * fg), 0});
   return out;
 }
 
@@ -196,7 +188,7 @@ inline std::vector<FeatGroup> equal_groups4(int n) {
   if (n <= 0) return out;
   const int ng = std::max(1, (n + 63) / 64);
   const int fg = std::min(64, ((n + ng - 1) / ng + 3) / 4 * 4);
-  for (int gi = 0; gi * fg < n; ++gi) out.push_back(FeatGroup{gi * fg, std::min(fg, n - gi * fg), false, false});
+  for (int gi = 0; gi * fg < n; ++gi) out.push_back(FeatGroup{gi * fg, std::min(fg, n - gi * fg), 0});
   return out;
 }
 
@@ -267,17 +259,17 @@ GroupLayout group_layout(const GrowArgs& a, bool use_subset, bool fp) {
         for (int i = 1; ok && i < g.nf; ++i) ok = perm_feats[g.f0 + i] == perm_feats[g.f0] + i;
         // with a compact histogram matrix every wide group must lie inside it (the kernel reads Xh only)
         if (ok && a.Xh != nullptr) ok = a.Fh % 4 == 0 && perm_feats[g.f0] + g.nf <= a.Fh;
-        g.wide = ok;
+        if (ok) g.flags |= TMOG_ITEM_WIDE;   // contiguous dword-aligned physical columns
       }
       full_groups.push_back(g);
     }
     const int n_one = o1 - o0;
     if (GPU && a.csr_ptr && a.csr_col && n_multi > 0 && n_one > 0 && a.csr_nf == n_one &&
         2 * n_one + 4 + 64 * 4 <= 64 * (B * S + 1))   // sums + list lengths of the CSR item (tree_kernels.hip)
-      full_groups.push_back(FeatGroup{n_multi, n_one, false, true});   // one item walks the rows' CSR lists
+      full_groups.push_back(FeatGroup{n_multi, n_one, TMOG_ITEM_CSR});   // one item walks the rows' CSR lists
     else
       for (const FeatGroup& g : equal_groups(n_one))
-        full_groups.push_back(FeatGroup{n_multi + g.f0, g.nf, GPU, false});
+        full_groups.push_back(FeatGroup{n_multi + g.f0, g.nf, GPU ? TMOG_ITEM_REG : 0});
   } else if (fp) {
     if (a.fp_mlo < 0 || a.fp_mhi > F || a.fp_mhi <= a.fp_mlo) throw std::runtime_error("bad feature-parallel slice");
     for (int f = a.fp_mlo; f < a.fp_mhi; ++f) perm_feats.push_back(f);
@@ -339,17 +331,9 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
     std::vector<LeafItemH> items;
     for (int64_t i : idx) {
       const int64_t c = lv_count[i];
-      if (c <= 0) continue;
-      for (int64_t o = 0; o < c; o += a.chunk_rows) {
-        LeafItemH it;
-        it.begin = lv_begin[i] + o;
-        it.count = std::min(a.chunk_rows, c - o);
-        it.out = leaf_pos + o;
-        it.gid = (int32_t)lv_gid[i];
-        it.buf = 0;
-        items.push_back(it);
-      }
-      leaf_pos += c;
+      for (int64_t k = 0, nl = leaf_items(c, a.chunk_rows); k < nl; ++k)
+        items.push_back(leaf_item_at(k, lv_begin[i], c, a.chunk_rows, leaf_pos, (int32_t)lv_gid[i], 0));
+      leaf_pos += std::max<int64_t>(c, 0);
     }
     if (items.empty()) return;
     st3.clear();
@@ -391,23 +375,24 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
     const int64_t n = (int64_t)lv_gid.size();
     if (n == 0) break;
     if (timing) t_lvl = tclock::now();
-    std::vector<uint8_t> can(n), need(n);
+    std::vector<int> flags(n);   // kNode* bits (common/tree_plan.hpp)
     std::vector<int64_t> hist_nodes;
-    for (int64_t i = 0; i < n; ++i) {
+    auto can = [&](int64_t i) {
       const int t = (int)lv_tree[i];
       const bool gate = newton && depth > 0;   // the hessian: the node's second total, from its parent's split
-      can[i] = can_split(depth, a.job_depth[j0 + t], lv_count[i], a.job_min_inst[j0 + t], gate, a.job_mcw[j0 + t],
-                         gate ? R.tot[(size_t)lv_gid[i] * S + 1] : 0.0);
-      need[i] = can[i] || depth == 0;
-    }
-    // a splittable node whose sibling cannot split still gets its histogram by subtraction from the
-    // parent's: build the sibling's (scan skipped: its may-split slot is 0) rather than the node's own
-    if (a.subtract && !use_subset && prev_hist && depth > 0)
+      return can_split(depth, a.job_depth[j0 + t], lv_count[i], a.job_min_inst[j0 + t], gate, a.job_mcw[j0 + t],
+                       gate ? R.tot[(size_t)lv_gid[i] * S + 1] : 0.0);
+    };
+    // subtraction trick: children come in (left, right) pairs
+    const bool subtract = a.subtract && !use_subset && prev_hist && depth > 0;
+    if (depth == 0)
+      for (int64_t i = 0; i < n; ++i) flags[i] = root_flags(can(i));
+    else
       for (int64_t q = 0; 2 * q + 1 < n; ++q)
-        if (build_sibling(can[2 * q], need[2 * q], lv_count[2 * q], need[2 * q + 1], lv_count[2 * q + 1]))
-          need[2 * q] = need[2 * q + 1] = 1;
+        sibling_flags(can(2 * q), can(2 * q + 1), lv_count[2 * q], lv_count[2 * q + 1], subtract, &flags[2 * q],
+                      &flags[2 * q + 1]);
     for (int64_t i = 0; i < n; ++i)
-      if (need[i]) hist_nodes.push_back(i);
+      if (flags[i] & kNodeNeed) hist_nodes.push_back(i);
     if (hist_nodes.empty()) {
       std::vector<int64_t> all(n);
       for (int64_t i = 0; i < n; ++i) all[i] = i;
@@ -447,20 +432,16 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
     hist = bk.hist_buffer(cur_slot, (size_t)hwords);
     std::vector<int64_t> loc(n, -1);
     for (int j = 0; j < m; ++j) loc[hist_nodes[j]] = j;
-    // ---- subtraction trick: children come in (left, right) pairs
+    // ---- sibling pairs: the big node is derived from the parent's histogram and the small node's
     std::vector<int64_t> d_big, d_small, d_poff;
-    if (a.subtract && !use_subset && prev_hist && depth > 0) {
-      for (int64_t q = 0; 2 * q + 1 < n; ++q) {
-        const int64_t li = 2 * q, ri = 2 * q + 1;
-        if (!(need[li] && need[ri])) continue;
-        const bool left_big = left_is_big(lv_count[li], lv_count[ri]);
-        d_big.push_back(loc[left_big ? li : ri]);
-        d_small.push_back(loc[left_big ? ri : li]);
-        d_poff.push_back(pair_parent_off[q]);
-      }
+    for (int64_t q = 0; 2 * q + 1 < n; ++q) {
+      const int64_t li = 2 * q, ri = 2 * q + 1;
+      if (!(flags[li] & kNodePairLeft)) continue;
+      const bool left_big = flags[li] & kNodeDerived;
+      d_big.push_back(loc[left_big ? li : ri]);
+      d_small.push_back(loc[left_big ? ri : li]);
+      d_poff.push_back(pair_parent_off[q]);
     }
-    std::vector<uint8_t> build(m, 1);
-    for (int64_t b : d_big) build[b] = 0;
     // GPU: a sibling pair's subtraction and both children's split scans run as one pass (pair_scan_kernel)
     // -- the two nodes are flagged (paired slot) so the node-wise scan skips them; same decisions
     const char* ps_env = std::getenv("TMOG_PAIR_SCAN");
@@ -481,89 +462,55 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
       nb[j] = lv_begin[i];
       nc[j] = lv_count[i];
       nmd[j] = a.job_model[j0 + t];
-      float* P = &params[(size_t)j * kPrmStride];
-      P[kPrmMinInst] = (float)a.job_min_inst[j0 + t];
-      P[kPrmMinGain] = (float)a.job_min_gain[j0 + t];
-      P[kPrmMcw] = (float)a.job_mcw[j0 + t];
-      P[kPrmLambda] = (float)a.job_lambda[j0 + t];
-      P[kPrmAllowMissing] = a.missing_bin >= 0 ? 1.f : 0.f;
-      P[kPrmEps] = (float)a.job_eps[j0 + t];
-      P[kPrmMaySplit] = can[i] ? 1.f : 0.f;
+      fill_node_params(&params[(size_t)j * kPrmStride], a.job_min_inst[j0 + t], a.job_min_gain[j0 + t],
+                       a.job_mcw[j0 + t], a.job_lambda[j0 + t], pair_fuse && (flags[i & ~(int64_t)1] & kNodePairLeft),
+                       a.missing_bin >= 0, a.job_eps[j0 + t], flags[i] & kNodeCan);
     }
-    for (size_t q = 0; q < d_sj.size(); ++q)
-      params[(size_t)d_sj[q] * kPrmStride + kPrmPaired] = params[(size_t)d_bj[q] * kPrmStride + kPrmPaired] = 1.f;
-    // ---- work items (GPU) / built-node arrays (CPU)
+    // ---- work items (GPU) / built-node arrays (CPU), laid out by common/tree_plan.hpp
     std::vector<HistItemH> hitems;
     std::vector<PartItemH> citems;
     std::vector<int64_t> z_off, z_size;
     std::vector<int64_t> zc_off, zc_size;   // nodes whose only multi-item group is the CSR one: zero its words
     std::vector<int64_t> b_nb, b_nc, b_nho;
     std::vector<int32_t> b_nfo, b_nnf, b_nmd;
+    std::vector<NodeWork> work(m);
+    std::vector<std::vector<FeatGroup>> sub_groups(use_subset ? m : 0);   // per-node subsets: groups of the node's own
+    auto groups_of = [&](int j) -> const std::vector<FeatGroup>& { return use_subset ? sub_groups[j] : full_groups; };
+    int n_wide = 0;
+    int64_t n_other = 0, n_general = 0;
     for (int j = 0; j < m; ++j) {
-      const int64_t cnt = nc[j];
-      const int64_t nch = std::max<int64_t>(1, (cnt + a.chunk_rows - 1) / a.chunk_rows);
-      // partition items: short slices (each is a chain of 256-row steps with cursor atomics)
-      for (int64_t c = 0, npi = std::max<int64_t>(1, (cnt + kPartRows - 1) / kPartRows); c < npi; ++c) {
-        PartItemH p;
-        p.node = j;
-        p.pad = 0;
-        p.begin = nb[j] + c * kPartRows;
-        p.count = std::min(kPartRows, cnt - c * kPartRows);
-        p.out_left = p.out_right = 0;
-        citems.push_back(p);
-      }
-      if (!build[j]) continue;
+      if (use_subset) sub_groups[j] = equal_groups(nfeat[j]);
+      const std::vector<FeatGroup>& grp = groups_of(j);
+      const NodeWork& w = work[j] = node_work(flags[hist_nodes[j]], nc[j], a.chunk_rows, grp.data(), (int)grp.size(),
+                                              n_sc, live_dense, hsz[j]);
+      for (int64_t k = 0; k < w.n_part; ++k) citems.push_back(part_item_at(j, k, nb[j], nc[j]));
+      if (flags[hist_nodes[j]] & kNodeDerived) continue;
       b_nb.push_back(nb[j]);
       b_nc.push_back(nc[j]);
       b_nho.push_back(hoff[j]);
       b_nfo.push_back(feat_off[j]);
       b_nnf.push_back(nfeat[j]);
       b_nmd.push_back(nmd[j]);
-      const int nf = nfeat[j];
-      const std::vector<FeatGroup>& grp = use_subset ? equal_groups(nf) : full_groups;
-      // CSR items take kCsrRows-row slices (each walks its rows one at a time, so shorter items keep
-      // more of them in flight); a node split over several items is zeroed and accumulated atomically
-      const int64_t ncsr = std::max<int64_t>(1, (cnt + kCsrRows - 1) / kCsrRows);
-      bool has_csr = false;
-      for (const FeatGroup& fgp : grp) has_csr |= fgp.csr;
-      if (nch > 1) {
-        z_off.push_back(hoff[j]);
-        z_size.push_back(hsz[j]);
-      } else if (has_csr && ncsr > 1) {
-        // single-chunk multi-bin groups write their words exclusively: only the one-present-bin region
-        // past the dense prefix (the CSR group's bin-0 words) accumulates atomically and needs zeroing
-        if (live_dense >= 0 && live_dense < hsz[j]) {
-          zc_off.push_back(hoff[j] + live_dense);
-          zc_size.push_back(hsz[j] - live_dense);
-        } else {
-          z_off.push_back(hoff[j]);
-          z_size.push_back(hsz[j]);
-        }
+      if (w.zero != kZeroNone) {
+        int64_t zo, zs;
+        zero_segment(w.zero, hoff[j], hsz[j], live_dense, &zo, &zs);
+        (w.zero == kZeroCsr ? zc_off : z_off).push_back(zo);
+        (w.zero == kZeroCsr ? zc_size : z_size).push_back(zs);
       }
-      for (const FeatGroup& fgp : grp) {
-        const int64_t step = fgp.csr ? kCsrRows : a.chunk_rows;
-        const int64_t nit = fgp.csr ? ncsr : nch;
-        const int nchunk = (fgp.csr || fgp.reg) ? 1 : n_sc;
-        for (int sc = 0; sc < nchunk; ++sc)
-          for (int64_t c = 0; c < nit; ++c) {
-            HistItemH h;
-            h.node = j;
-            h.fg0 = fgp.f0;
-            h.nf = fgp.nf;
-            h.excl = (nit == 1 ? 1 : 0) | (fgp.reg ? 2 : 0) | (fgp.csr ? 4 : 0) | (fgp.wide ? 16 : 0) |
-                     ((fgp.reg || fgp.csr) && live_dense >= 0 ? 8 : 0) | (sc << 8);
-            h.begin = nb[j] + c * step;
-            h.count = std::min(step, cnt - c * step);
-            hitems.push_back(h);
-          }
-      }
+      n_wide += (int)w.n_wide;
+      n_other += w.n_other;
+      n_general += w.n_general;
     }
     // wide-load items first: the GPU launches them as a kernel of their own (fewer registers)
-    const auto wide_end = std::stable_partition(hitems.begin(), hitems.end(),
-                                                [](const HistItemH& h) { return (h.excl & 16) != 0; });
-    const int n_wide = (int)(wide_end - hitems.begin());
-    int need_general = 0;          // any item on the byte-gather path (not CSR, not wide-load)?
-    for (const HistItemH& h : hitems) need_general |= (h.excl & (4 | 16)) == 0;
+    hitems.reserve((size_t)(n_wide + n_other));
+    for (const bool wide : {true, false})
+      for (int j = 0; j < m; ++j) {
+        const std::vector<FeatGroup>& grp = groups_of(j);
+        for (int64_t k = 0, nk = wide ? work[j].n_wide : work[j].n_other; k < nk; ++k)
+          hitems.push_back(hist_item_at(wide, j, k, nb[j], nc[j], a.chunk_rows, grp.data(), (int)grp.size(), n_sc,
+                                        live_dense));
+      }
+    const int need_general = n_general > 0;   // any item on the byte-gather path (not CSR, not wide-load)?
     std::vector<int64_t> d_soff, d_ooff, d_size;
     int64_t d_max = 0;
     for (size_t q = 0; q < d_big.size(); ++q) {

@@ -116,14 +116,14 @@ __device__ __forceinline__ void add_row(int* my, int bin, int S, int s0, int Sc,
 // the histogram stays bit-identical to the CPU twin). Masking lanes does not shorten an LDS atomic
 // wave-instruction, so this alone saves little; what it enables is the register path below.
 //
-// Register path (excl bit 1, sparse mode only): when every feature of the group has a single present
+// Register path (TMOG_ITEM_REG, sparse mode only): when every feature of the group has a single present
 // bin (one-hot and null-indicator columns under ``missing`` = 0: value 1 -> bin 0, value 0 -> missing
 // bin) a lane just sums the (g, h) of its rows with bin 0 in two registers -- no LDS atomics in the
 // row loop at all, one per lane at the end. The tree grower groups such columns together
 // (common/tree_grow.hpp), so on the headline table ~40 % of the feature groups skip the atomics.
 // PMC on the tree micro-benchmark: ~0.064 LDS wave-instructions per CU-cycle at ~11 cycles each for
 // a ds_add_u32 -> the LDS atomic unit is ~70 % busy; VALU ~12 % busy, so trading atomics for VALU pays.
-// CSR path (excl bit 2, MODE 2 with a sparse missing bin): one item covers ALL one-present-bin columns
+// CSR path (TMOG_ITEM_CSR, MODE 2 with a sparse missing bin): one item covers ALL one-present-bin columns
 // of a node row-chunk. Such a column's histogram has two non-zero bins -- the present bin 0 and the
 // missing bin -- and the missing bin is the chunk total minus bin 0, so only the entries with bin 0
 // matter: the row's CSR list (csr_ptr / csr_col, local column ids). The wave walks its 64 staged
@@ -298,7 +298,7 @@ __device__ __forceinline__ void hist_csr_item(const HistItem& it, const uint32_t
   // hist_subtract maintain only that word, so no other word of these columns is ever live.
   int64_t* out = hist + node_hist_off[it.node] + (int64_t)it.fg0 * B * S;
   const int per = B * S;
-  const bool excl = (it.excl & 1) != 0;
+  const bool excl = (it.excl & TMOG_ITEM_SOLE) != 0;
   for (int k = threadIdx.x; k < nf * S; k += blockDim.x) {
     const int f = k / S, s = k - f * S;
     const int v = s ? a1[f] : a0[f];
@@ -309,7 +309,7 @@ __device__ __forceinline__ void hist_csr_item(const HistItem& it, const uint32_t
 }
 
 
-// Wide-load path (MODE 2, excl bit 4): a dense group of FG <= 64 multi-bin columns that are physically
+// Wide-load path (MODE 2, TMOG_ITEM_WIDE): a dense group of FG <= 64 multi-bin columns that are physically
 // contiguous and dword aligned in Xb (col0 % 4 == 0, row stride % 4 == 0; the XGBoost learner pads its
 // growth-order matrix to that). Lane (rs, d) loads dword d of the group's row segment -- 4 bins of one
 // row in one 4-byte load -- so a wave-instruction covers 64 / ceil(FG/4) rows (4 for FG = 64) and
@@ -470,7 +470,7 @@ __device__ __forceinline__ void hist_wide_item(const HistItem& it, const uint8_t
     __syncthreads();
   }
   int64_t* out = hist + node_hist_off[it.node] + (int64_t)it.fg0 * B * 2;
-  const bool excl = (it.excl & 1) != 0;
+  const bool excl = (it.excl & TMOG_ITEM_SOLE) != 0;
   for (int k = threadIdx.x; k < FG * B; k += blockDim.x) {
     const int f = k / B, b = k - f * B;
     const unsigned long long v = tab[tix(f, (sparse && b == skip_bin) ? B : b)];
@@ -527,18 +527,18 @@ __global__ void __launch_bounds__(256) hist_build_kernel(
   // dcount (device-planned levels, tree_resident.hip): the grid is an upper bound, the item count is on the device
   if (dcount != nullptr && (int)blockIdx.x >= *dcount) return;
   const HistItem it = items[blockIdx.x];
-  const int s0 = ((it.excl >> 8) & 0xFF) * Sc;   // statistic chunk of this item (excl bits 8..15)
+  const int s0 = ((it.excl >> TMOG_ITEM_SC_SHIFT) & 0xFF) * Sc;   // statistic chunk of this item
   const int sc = min(Sc, S - s0);
   if (MODE == 2 && g_hist_debug) {
-    if ((g_hist_debug & 1) && (it.excl & 4)) return;
-    if ((g_hist_debug & 2) && !(it.excl & 4)) return;
+    if ((g_hist_debug & 1) && (it.excl & TMOG_ITEM_CSR)) return;
+    if ((g_hist_debug & 2) && !(it.excl & TMOG_ITEM_CSR)) return;
   }
-  if (MODE == 2 && (it.excl & 4)) {
+  if (MODE == 2 && (it.excl & TMOG_ITEM_CSR)) {
     hist_csr_item(it, rows, node_model, node_hist_off, hist, B, S, t1, t2, stride, qscale, skip_bin, csr_ptr,
                   csr_col, lds, gh, wide);
     return;
   }
-  if (MODE == 2 && (it.excl & 16)) {        // wide-load items read the compact matrix (GrowArgs.Xh, or Xb)
+  if (MODE == 2 && (it.excl & TMOG_ITEM_WIDE)) {        // wide-load items read the compact matrix (GrowArgs.Xh, or Xb)
     hist_wide_item(it, Xh, Fh, feat_list[node_feat_off[it.node] + it.fg0], rows, node_model, node_hist_off, hist, B,
                    t1, t2, stride, qscale, skip_bin, lds, gh, wide);
     return;
@@ -556,8 +556,8 @@ __global__ void __launch_bounds__(256) hist_build_kernel(
   int4* stage = reinterpret_cast<int4*>(lds + ((ncopy_words + 3) & ~3)) + wave * 64;
   int* tot = lds + ((ncopy_words + 3) & ~3) + 4 * 64 * 4;     // chunk totals (sparse missing bin)
   const bool sparse = MODE == 2 && skip_bin >= 0;
-  const bool regacc = sparse && (it.excl & 2);
-  const bool excl = (it.excl & 1) != 0;
+  const bool regacc = sparse && (it.excl & TMOG_ITEM_REG);
+  const bool excl = (it.excl & TMOG_ITEM_SOLE) != 0;
   for (int i = threadIdx.x; i < ncopy_words; i += blockDim.x) lds[i] = 0;
   if (threadIdx.x < TM_MAX_S) tot[threadIdx.x] = 0;
   __syncthreads();
@@ -659,9 +659,9 @@ __global__ void __launch_bounds__(256) hist_build_kernel(
       row[skip_bin * S + s] = tot[s] - sum;
     }
     __syncthreads();
-    // excl bit 3: the group's columns have one present bin and only their bin 0 is live (the grower
+    // TMOG_ITEM_LIVE0: the group's columns have one present bin and only their bin 0 is live (the grower
     // orders multi-bin columns first and zero / subtract maintain bin 0 alone, see hist_csr_item)
-    const int wlimit = (it.excl & 8) ? S : B * S;
+    const int wlimit = (it.excl & TMOG_ITEM_LIVE0) ? S : B * S;
     for (int k = threadIdx.x; k < words; k += blockDim.x) {
       const int f = k / (B * S);
       if (k - f * (B * S) >= wlimit) continue;

@@ -11,11 +11,11 @@
 // without a single synchronisation, and boosting (models/trees.py) enqueues round after round. The host
 // reads the created-node records once per fit.
 //
-// The device plan reproduces grow_group's decisions exactly (same can / need rules, Newton hessian gate,
-// subtraction pairing, feature groups from group_layout, item chunking), so the trees are bit-identical
-// to the host-planned grower (tests/test_tree_resident_gpu.py); work-item ORDER may differ where it does not
-// matter (integer histogram atomics and exclusive stores are order-independent, partition order inside a
-// child is not stable on either path).
+// The device plan reproduces grow_group's decisions exactly: both evaluate common/tree_rules.hpp (can / need rules,
+// Newton hessian gate) and common/tree_plan.hpp (subtraction pairing, work counts, items, zero segments, parameter
+// slots) over the feature groups of group_layout, so the trees are bit-identical to the host-planned grower
+// (tests/test_tree_resident_gpu.py; the layout alone: tests/test_level_items_cpu.py). Partition order inside a
+// child is not stable on either path.
 //
 // Reference behaviour: XGBoost4J's hist updater as wrapped by OpXGBoostClassifier.scala:47-403.
 #include <hip/hip_runtime.h>
@@ -60,7 +60,7 @@ constexpr int kRecFixed = TMOG_REC_FIXED;   // record words before the S totals:
 struct PlanArgs {
   int d, T, S, chunk_rows, n_groups, n_sc, newton, subtract, pair_fuse, F_use, has_missing;
   int64_t hsz, live_dense;
-  const int4* groups;          // (f0, nf, flags): bit 0 register path, bit 1 CSR, bit 2 wide-load
+  const tmog::FeatGroup* groups;   // GroupLayout.full_groups as they are
   const int32_t* j_depth;
   const int32_t* j_model;
   const int64_t* j_count;
@@ -198,8 +198,6 @@ __device__ __forceinline__ void init_node(int64_t* r, int64_t tree, int S) {
   for (int s = 0; s < S; ++s) r[kRecFixed + s] = dbits(0.0);
 }
 
-__device__ __forceinline__ int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // Leaf items of the nodes i in [0, n) whose sa-flag is 0 (sa == nullptr: all nodes), reading buffer `buf`.
 // Appends to litems at C_NL and advances the leaf cursor (host twin: the collect lambda of grow_group).
 // The planner's per-node scratch arrays (global memory, or dynamic LDS when the level capacity fits).
@@ -216,7 +214,7 @@ __device__ void emit_leaves(const PlanArgs& A, const PlanScratch& Z, int lvl, in
     const bool leaf = split == nullptr || split[i] == 0;
     const int64_t c = cnt_[i];
     Z.sd[i] = leaf && c > 0 ? c : 0;
-    Z.se[i] = leaf && c > 0 ? cdiv(c, A.chunk_rows) : 0;
+    Z.se[i] = leaf ? tmog::leaf_items(c, A.chunk_rows) : 0;
   }
   __syncthreads();
   const int64_t lbase = *A.leaf_pos;
@@ -229,14 +227,8 @@ __device__ void emit_leaves(const PlanArgs& A, const PlanScratch& Z, int lvl, in
   const int64_t n_emit = min(tot_items, A.cap_l - nl0);
   for (int64_t k = t; k < n_emit; k += nt) {
     const int64_t i = owner(Z.se, n, k);
-    const int64_t o = (k - Z.se[i]) * A.chunk_rows;
-    LeafItemH it;
-    it.begin = A.lv_begin[lvl][i] + o;
-    it.count = min((int64_t)A.chunk_rows, cnt_[i] - o);
-    it.out = lbase + Z.sd[i] + o;
-    it.gid = A.lv_gid[lvl][i];
-    it.buf = buf;
-    A.litems[nl0 + k] = it;
+    A.litems[nl0 + k] = tmog::leaf_item_at(k - Z.se[i], A.lv_begin[lvl][i], cnt_[i], A.chunk_rows, lbase + Z.sd[i],
+                                           A.lv_gid[lvl][i], buf);
   }
   __syncthreads();
   if (t == 0) {
@@ -339,7 +331,7 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
       const int64_t c = pcnt[i];
       const bool leaf = !split && c > 0;
       Z.sd[i] = leaf ? c : 0;
-      Z.se[i] = leaf ? cdiv(c, A.chunk_rows) : 0;
+      Z.se[i] = split ? 0 : tmog::leaf_items(c, A.chunk_rows);
       Z.sf[i] = split ? 1 : 0;
       Z.flag[i] = split ? 1 : 0;
     }
@@ -365,14 +357,8 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
     const int64_t n_emit = min(tot_items, A.cap_l - nl0);
     for (int64_t k = t; k < n_emit; k += nt) {
       const int64_t i = owner(Z.se, n_prev, k);
-      const int64_t o = (k - Z.se[i]) * A.chunk_rows;
-      LeafItemH it;
-      it.begin = A.lv_begin[P][i] + o;
-      it.count = min((int64_t)A.chunk_rows, pcnt[i] - o);
-      it.out = lbase + Z.sd[i] + o;
-      it.gid = A.lv_gid[P][i];
-      it.buf = P;
-      A.litems[nl0 + k] = it;
+      A.litems[nl0 + k] = tmog::leaf_item_at(k - Z.se[i], A.lv_begin[P][i], pcnt[i], A.chunk_rows, lbase + Z.sd[i],
+                                             A.lv_gid[P][i], P);
     }
     // (c) splits -> records + children (level d), in split order
     for (int i = t; i < n_prev; i += nt) {
@@ -429,13 +415,12 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
     }
     return;
   }
-  // ---- plan level d, one pass over sibling pairs (level 0: over the roots). Per node i: flag bits
-  // 1 = can split, 2 = needs a histogram, 4 = left node of a histogram pair, 8 = the pair's derived (big) node;
-  // counts for one multi-scan: sa need, sb wide-load hist items, sc other hist items, sd partition items,
-  // se whole-node zero segments, sf CSR-region zero segments, sg pairs (at the left node)
+  // ---- plan level d, one pass over sibling pairs (level 0: over the roots). Per node i: the kNode* flag bits
+  // and work counts of common/tree_plan.hpp, the counts for one multi-scan: sa need, sb wide-load hist items,
+  // sc other hist items, sd partition items, se whole-node zero segments, sf CSR-region zero segments, sg pairs (at
+  // the left node)
   const int32_t* ltree = A.lv_tree[C];
   const int64_t* lcnt = A.lv_count[C];
-  const bool dense_split = A.live_dense >= 0 && A.live_dense < A.hsz;
   auto can_split = [&](int i) {
     const int jt = ltree[i];
     const bool gate = A.newton && d > 0;       // the hessian: the node's second total, recorded by its parent's split
@@ -443,45 +428,26 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
                            gate ? bitsd(R(A.lv_gid[C][i])[kRecFixed + 1]) : 0.0);
   };
   auto counts = [&](int i, int fl) {
-    const bool need = fl & 2;
-    const int64_t c = lcnt[i];
-    const int64_t nch = max((int64_t)1, cdiv(c, A.chunk_rows));
-    const int64_t ncsr = max((int64_t)1, cdiv(c, tmog::kCsrRows));
-    const bool build = need && !(fl & 8);
-    int64_t wide = 0, other = 0;
-    bool has_csr = false;
-    if (build)
-      for (int g = 0; g < A.n_groups; ++g) {
-        const int gfl = A.groups[g].z;
-        const bool reg = gfl & 1, csr = gfl & 2, wd = gfl & 4;
-        const int64_t k = (csr ? ncsr : nch) * ((csr || reg) ? 1 : A.n_sc);
-        if (wd) wide += k;
-        else other += k;
-        has_csr |= csr;
-      }
+    const tmog::NodeWork w = tmog::node_work(fl, lcnt[i], A.chunk_rows, A.groups, A.n_groups, A.n_sc, A.live_dense,
+                                             A.hsz);
     Z.flag[i] = fl;
-    Z.sa[i] = need ? 1 : 0;
-    Z.sb[i] = wide;
-    Z.sc[i] = other;
-    Z.sd[i] = need ? max((int64_t)1, cdiv(c, tmog::kPartRows)) : 0;
-    Z.se[i] = build && (nch > 1 || (has_csr && ncsr > 1 && !dense_split)) ? 1 : 0;
-    Z.sf[i] = build && nch == 1 && has_csr && ncsr > 1 && dense_split ? 1 : 0;
-    Z.sg[i] = (fl & 4) ? 1 : 0;
+    Z.sa[i] = (fl & tmog::kNodeNeed) ? 1 : 0;
+    Z.sb[i] = w.n_wide;
+    Z.sc[i] = w.n_other;
+    Z.sd[i] = w.n_part;
+    Z.se[i] = w.zero == tmog::kZeroNode ? 1 : 0;
+    Z.sf[i] = w.zero == tmog::kZeroCsr ? 1 : 0;
+    Z.sg[i] = (fl & tmog::kNodePairLeft) ? 1 : 0;
   };
   if (d == 0) {
-    for (int i = t; i < n; i += nt) counts(i, (can_split(i) ? 1 : 0) | 2);
+    for (int i = t; i < n; i += nt) counts(i, tmog::root_flags(can_split(i)));
   } else {
     for (int q = t; 2 * q + 1 < n; q += nt) {
       const int li = 2 * q, ri = li + 1;
-      const bool cl = can_split(li), cr = can_split(ri);
-      bool nl = cl, nr = cr;
-      // subtraction pairing: when one sibling needs a histogram, the other gets one too if it is the smaller
-      // (built) one -- then the bigger one is derived from the parent
-      if (tmog::build_sibling(cl, nl, lcnt[li], nr, lcnt[ri])) nl = nr = true;
-      const bool pair = nl && nr;
-      const bool left_big = tmog::left_is_big(lcnt[li], lcnt[ri]);
-      counts(li, (cl ? 1 : 0) | (nl ? 2 : 0) | (pair ? 4 : 0) | (pair && left_big ? 8 : 0));
-      counts(ri, (cr ? 1 : 0) | (nr ? 2 : 0) | (pair && !left_big ? 8 : 0));
+      int fl, fr;
+      tmog::sibling_flags(can_split(li), can_split(ri), lcnt[li], lcnt[ri], A.subtract != 0, &fl, &fr);
+      counts(li, fl);
+      counts(ri, fr);
     }
   }
   __syncthreads();
@@ -513,7 +479,7 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
   // ---- emission: per-node tables (histogram node j = need prefix, in node order), pairs, zero segments
   for (int i = t; i < n; i += nt) {
     const int fl = Z.flag[i];
-    if (!(fl & 2)) {
+    if (!(fl & tmog::kNodeNeed)) {
       A.loc[i] = -1;
       continue;
     }
@@ -527,19 +493,14 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
     A.nc[C][j] = lcnt[i];
     A.nfo[j] = 0;
     A.nnf[j] = A.F_use;
-    const bool paired = d > 0 && (((i & 1) == 0 && (fl & 4)) || ((i & 1) == 1 && (Z.flag[i - 1] & 4)));
-    float* Pp = A.par[C] + (int64_t)j * tmog::kPrmStride;
-    Pp[tmog::kPrmMinInst] = (float)A.j_inst[jt];
-    Pp[tmog::kPrmMinGain] = (float)A.j_gain[jt];
-    Pp[tmog::kPrmMcw] = (float)A.j_mcw[jt];
-    Pp[tmog::kPrmLambda] = (float)A.j_lam[jt];
-    Pp[tmog::kPrmPaired] = paired ? 1.f : 0.f;             // pair_fuse: the pair scan derives / scans both siblings
-    Pp[tmog::kPrmAllowMissing] = A.has_missing ? 1.f : 0.f;
-    Pp[tmog::kPrmEps] = (float)A.j_eps[jt];
-    Pp[tmog::kPrmMaySplit] = (fl & 1) ? 1.f : 0.f;
-    if (fl & 4) {                          // left node of a pair: (small, big) histogram nodes, parent offset
+    // pair_fuse: the pair scan derives / scans both siblings
+    const bool paired = d > 0 && (((i & 1) == 0 && (fl & tmog::kNodePairLeft)) ||
+                                  ((i & 1) == 1 && (Z.flag[i - 1] & tmog::kNodePairLeft)));
+    tmog::fill_node_params(A.par[C] + (int64_t)j * tmog::kPrmStride, A.j_inst[jt], A.j_gain[jt], A.j_mcw[jt],
+                           A.j_lam[jt], paired, A.has_missing != 0, A.j_eps[jt], (fl & tmog::kNodeCan) != 0);
+    if (fl & tmog::kNodePairLeft) {        // left node of a pair: (small, big) histogram nodes, parent offset
       const int jr = (int)Z.sa[i + 1];
-      const bool left_big = fl & 8;
+      const bool left_big = fl & tmog::kNodeDerived;
       const int64_t k = Z.sg[i];
       A.sj[k] = left_big ? jr : j;
       A.bj[k] = left_big ? j : jr;
@@ -547,66 +508,27 @@ __global__ void __launch_bounds__(1024) level_plan_kernel(PlanArgs A) {
     }
     const bool zw = (i + 1 < n ? Z.se[i + 1] : n_zw) != Z.se[i];
     const bool zc = (i + 1 < n ? Z.sf[i + 1] : n_zc) != Z.sf[i];
-    if (zw) {
-      A.zoff[Z.se[i]] = (int64_t)j * A.hsz;
-      A.zsize[Z.se[i]] = A.hsz;
-    }
-    if (zc) {
-      A.zoff[n_zw + Z.sf[i]] = (int64_t)j * A.hsz + A.live_dense;
-      A.zsize[n_zw + Z.sf[i]] = A.hsz - A.live_dense;
-    }
+    const int64_t hoff = (int64_t)j * A.hsz;
+    if (zw) tmog::zero_segment(tmog::kZeroNode, hoff, A.hsz, A.live_dense, &A.zoff[Z.se[i]], &A.zsize[Z.se[i]]);
+    if (zc)
+      tmog::zero_segment(tmog::kZeroCsr, hoff, A.hsz, A.live_dense, &A.zoff[n_zw + Z.sf[i]], &A.zsize[n_zw + Z.sf[i]]);
   }
   mark(6);
   const int64_t n_hist = n_wide + n_other;
   const int64_t h_emit = min(n_hist, A.cap_h), c_emit = min(n_part, A.cap_c);
-  // histogram items, wide-load items first (the host's stable partition), then the others
+  // histogram items, wide-load items first (a kernel of their own), then the others
   for (int64_t k = t; k < h_emit; k += nt) {
     const bool wsec = k < n_wide;
     const int64_t* pre = wsec ? Z.sb : Z.sc;
     const int64_t kk = wsec ? k : k - n_wide;
     const int64_t i = owner(pre, n, kk);
-    int64_t local = kk - pre[i];
-    const int64_t c = lcnt[i];
-    const int64_t nch = max((int64_t)1, cdiv(c, A.chunk_rows));
-    const int64_t ncsr = max((int64_t)1, cdiv(c, tmog::kCsrRows));
-    const int64_t b0 = A.lv_begin[C][i];
-    const int32_t j = (int32_t)Z.sa[i];
-    for (int g = 0; g < A.n_groups; ++g) {
-      const int4 gr = A.groups[g];
-      const bool reg = gr.z & 1, csr = gr.z & 2, wd = gr.z & 4;
-      if (wd != wsec) continue;
-      const int64_t nit = csr ? ncsr : nch;
-      const int64_t nchunk = (csr || reg) ? 1 : A.n_sc;
-      if (local >= nit * nchunk) {
-        local -= nit * nchunk;
-        continue;
-      }
-      const int64_t sc_ = local / nit, ci = local - sc_ * nit;
-      const int64_t step = csr ? tmog::kCsrRows : A.chunk_rows;
-      HistItemH h;
-      h.node = j;
-      h.fg0 = gr.x;
-      h.nf = gr.y;
-      h.excl = (nit == 1 ? 1 : 0) | (reg ? 2 : 0) | (csr ? 4 : 0) | (wd ? 16 : 0) |
-               ((reg || csr) && A.live_dense >= 0 ? 8 : 0) | (int32_t)(sc_ << 8);
-      h.begin = b0 + ci * step;
-      h.count = min(step, c - ci * step);
-      A.hitems[k] = h;
-      break;
-    }
+    A.hitems[k] = tmog::hist_item_at(wsec, (int32_t)Z.sa[i], kk - pre[i], A.lv_begin[C][i], lcnt[i], A.chunk_rows,
+                                     A.groups, A.n_groups, A.n_sc, A.live_dense);
   }
   // partition items of every scanned node (kPartRows-row slices)
   for (int64_t k = t; k < c_emit; k += nt) {
     const int64_t i = owner(Z.sd, n, k);
-    const int64_t ci = k - Z.sd[i];
-    const int64_t c = lcnt[i];
-    PartItemH pi;
-    pi.node = (int32_t)Z.sa[i];
-    pi.pad = 0;
-    pi.begin = A.lv_begin[C][i] + ci * tmog::kPartRows;
-    pi.count = min((int64_t)tmog::kPartRows, c - ci * tmog::kPartRows);
-    pi.out_left = pi.out_right = 0;
-    A.citems[k] = pi;
+    A.citems[k] = tmog::part_item_at((int32_t)Z.sa[i], k - Z.sd[i], A.lv_begin[C][i], lcnt[i]);
   }
   if (t == 0) {
     A.cnt[C_N] = n;
@@ -778,6 +700,7 @@ struct Caps {
   int D = 0;
   std::vector<int64_t> nmax;   // nodes per level bound, d = 0..D + 1 (level D + 1 is empty)
   int64_t cap_nl = 0, cap_m = 0, cap_nodes = 0, cap_h = 0, cap_c = 0, cap_l = 0;
+  int64_t total = 0;           // row entries of the group
 };
 
 Caps caps_of(const tmog::GrowArgs& a, const tmog::GroupLayout& L, int n_sc) {
@@ -799,23 +722,11 @@ Caps caps_of(const tmog::GrowArgs& a, const tmog::GroupLayout& L, int n_sc) {
     c.cap_nodes += c.nmax[d];
   }
   c.cap_m = std::max<int64_t>(c.cap_m, 1);
-  for (const tmog::FeatGroup& g : L.full_groups) {
-    const int64_t step = g.csr ? tmog::kCsrRows : a.chunk_rows;
-    c.cap_h += ((g.csr || g.reg) ? 1 : n_sc) * (total / step + c.cap_m + 1);
-  }
-  c.cap_c = total / tmog::kPartRows + c.cap_m + 1;
-  c.cap_l = 2 * (total / std::max<int64_t>(a.chunk_rows, 1) + c.cap_nl + 1);
+  c.total = total;
+  c.cap_h = tmog::hist_items_bound(L.full_groups.data(), (int)L.full_groups.size(), a.chunk_rows, n_sc, total, c.cap_m);
+  c.cap_c = tmog::part_items_bound(total, c.cap_m);
+  c.cap_l = 2 * tmog::leaf_items_bound(a.chunk_rows, total, c.cap_nl);   // a plan collects two levels' leaves
   return c;
-}
-
-// per-level grid bounds
-int64_t hist_bound(const tmog::GrowArgs& a, const tmog::GroupLayout& L, int n_sc, int64_t total, int64_t m) {
-  int64_t h = 0;
-  for (const tmog::FeatGroup& g : L.full_groups) {
-    const int64_t step = g.csr ? tmog::kCsrRows : a.chunk_rows;
-    h += ((g.csr || g.reg) ? 1 : n_sc) * (total / step + m + 1);
-  }
-  return h;
 }
 
 // Configurations the device plan covers (everything else stays on the host-planned grower): one job group,
@@ -904,18 +815,16 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
     const int n_sc = 1;
     const Caps cp = caps_of(a, L, n_sc);
     if (io->cap_nodes < cp.cap_nodes) throw std::runtime_error("record buffer too small");
-    int64_t total = 0;
-    for (int j = 0; j < T; ++j) total += a.job_count[j];
+    const int64_t total = cp.total;
     const int F_use = L.F_use;
     const int64_t hsz = (int64_t)F_use * B * S;
     const int W = kRecFixed + S;
     // ---- per-call constants: groups, feature list, job table (shipped only when they change)
-    std::vector<int4> groups;
-    bool need_general = false;
-    for (const tmog::FeatGroup& g : L.full_groups) {
-      groups.push_back(make_int4(g.f0, g.nf, (g.reg ? 1 : 0) | (g.csr ? 2 : 0) | (g.wide ? 4 : 0), 0));
-      need_general |= !g.csr && !g.wide;
-    }
+    const std::vector<tmog::FeatGroup>& groups = L.full_groups;
+    const int n_groups = (int)groups.size();
+    // any item on the byte-gather path: that of a built node
+    const bool need_general = tmog::node_work(tmog::kNodeNeed, 1, a.chunk_rows, groups.data(), n_groups, n_sc,
+                                              L.live_dense, hsz).n_general > 0;
     std::vector<int32_t> flist(F_use);
     for (int f = 0; f < F_use; ++f) flist[f] = L.perm_feats.empty() ? f : L.perm_feats[f];
     tmog::Staging cs;
@@ -1037,7 +946,7 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
     P.T = T;
     P.S = S;
     P.chunk_rows = (int)a.chunk_rows;
-    P.n_groups = (int)groups.size();
+    P.n_groups = n_groups;
     P.n_sc = n_sc;
     P.newton = (a.mode == 2 && a.kind == 3 && S >= 2 && !(std::getenv("TMOG_TREE_HESS_GATE") &&
                                                             std::getenv("TMOG_TREE_HESS_GATE")[0] == '0')) ? 1 : 0;
@@ -1046,7 +955,7 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
     P.F_use = F_use;
     P.hsz = hsz;
     P.live_dense = L.live_dense;
-    P.groups = (const int4*)(K + o_groups);
+    P.groups = (const tmog::FeatGroup*)(K + o_groups);
     P.j_depth = (const int32_t*)(K + o_depth);
     P.j_model = (const int32_t*)(K + o_model);
     P.j_count = (const int64_t*)(K + o_count);
@@ -1099,8 +1008,8 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
       hipLaunchKernelGGL(level_plan_kernel, dim3(1), dim3(plan_nt), plan_lds, st, P);
       kchk((int)hipGetLastError(), "level_plan");
       const int64_t nprev = d > 0 ? cp.nmax[d - 1] : 0;
-      const int64_t lbound = (total / std::max<int64_t>(a.chunk_rows, 1) + nprev + 1) +
-                             (total / std::max<int64_t>(a.chunk_rows, 1) + cp.nmax[d] + 1);
+      const int64_t lbound = tmog::leaf_items_bound(a.chunk_rows, total, nprev) +
+                             tmog::leaf_items_bound(a.chunk_rows, total, cp.nmax[d]);
       kchk(tmog_hip_leaf_collect(rows[0], P.litems, (int)std::min(lbound, cp.cap_l), a.leaf_rows, a.leaf_gid, st,
                                  rows[1], cnt + C_NL),
            "leaf_collect");
@@ -1109,7 +1018,8 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
       const int64_t mb = cp.nmax[d];
       kchk(tmog_hip_zero_segments(hist[c], P.zoff, P.zsize, (int)mb, hsz, L.live_dense, B * S, S, st, 0, cnt + C_NZ),
            "zero_segments");
-      kchk(tmog_hip_hist_build(a.Xb, a.F, rows[c], P.hitems, (int)std::min(hist_bound(a, L, n_sc, total, mb), cp.cap_h),
+      const int64_t hb = tmog::hist_items_bound(groups.data(), n_groups, a.chunk_rows, n_sc, total, mb);
+      kchk(tmog_hip_hist_build(a.Xb, a.F, rows[c], P.hitems, (int)std::min(hb, cp.cap_h),
                                P.nfo, flist_d, P.nmd[c], P.nho[c], hist[c], B, a.mode, S, a.y, a.t1, a.t2, a.stride,
                                a.qscale, a.mode == 2 ? a.missing_bin : -1, a.csr_ptr, a.csr_col, S, 0,
                                need_general ? 1 : 0, st, use_gh ? gh[c] : nullptr, cnt + C_NH, a.wide_rows, a.Xh,
@@ -1137,7 +1047,7 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
              "fp_merge");
       }
       kchk(tmog_hip_partition_fused(a.Xb, a.F, rows[c], rows[c ^ 1], P.citems,
-                                    (int)std::min<int64_t>(total / tmog::kPartRows + mb + 1, cp.cap_c), P.nb[c],
+                                    (int)std::min(tmog::part_items_bound(total, mb), cp.cap_c), P.nb[c],
                                     P.nc[c], r_feat, r_bin, r_dl, P.par[c], r_gain, a.missing_bin, r_cur, a.XbT, a.N,
                                     st, use_gh ? gh[c] : nullptr, use_gh ? gh[c ^ 1] : nullptr, cnt + C_NC,
                                     a.wide_rows),

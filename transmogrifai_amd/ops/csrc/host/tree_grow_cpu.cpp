@@ -157,6 +157,45 @@ void tmog_grow_copy_cpu(void* h, int g, int64_t* tree, int64_t* feat, int64_t* b
 }
 void tmog_grow_free_cpu(void* h) { delete (tmog::GrowResult*)h; }
 
+void tmog_level_items_cpu(int n, const int64_t* count, const int64_t* begin, const int32_t* flags,
+                          const FeatGroup* groups, int n_groups, int64_t chunk_rows, int n_sc, int64_t live_dense,
+                          int64_t hsz, HistItem* hitems, PartItem* citems, LeafItem* litems, int64_t* z_off,
+                          int64_t* z_size, int64_t* totals) {
+  using namespace tmog;
+  auto work = [&](int i) { return node_work(flags[i], count[i], chunk_rows, groups, n_groups, n_sc, live_dense, hsz); };
+  int64_t nh = 0, nc = 0, nl = 0, zw = 0, zc = 0, n_wide = 0, n_general = 0, n_zw = 0, leaf_pos = 0;
+  for (int i = 0; i < n; ++i) n_zw += work(i).zero == kZeroNode;
+  for (const bool wide : {true, false}) {
+    int32_t j = 0;                                   // node slot: histogram nodes in node order
+    for (int i = 0; i < n; ++i) {
+      if (!(flags[i] & kNodeNeed)) continue;
+      const NodeWork w = work(i);
+      for (int64_t k = 0; k < (wide ? w.n_wide : w.n_other); ++k, ++nh)
+        if (hitems)
+          hitems[nh] = hist_item_at(wide, j, k, begin[i], count[i], chunk_rows, groups, n_groups, n_sc, live_dense);
+      if (wide) {                                    // once per node: partition items, zero segment, totals
+        for (int64_t k = 0; k < w.n_part; ++k, ++nc)
+          if (citems) citems[nc] = part_item_at(j, k, begin[i], count[i]);
+        if (w.zero != kZeroNone) {
+          const int64_t at = w.zero == kZeroNode ? zw++ : n_zw + zc++;   // whole-node segments first
+          if (z_off) zero_segment(w.zero, (int64_t)j * hsz, hsz, live_dense, &z_off[at], &z_size[at]);
+        }
+        n_wide += w.n_wide;
+        n_general += w.n_general;
+      }
+      ++j;
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    if (flags[i] & kNodeNeed) continue;
+    for (int64_t k = 0; k < leaf_items(count[i], chunk_rows); ++k, ++nl)
+      if (litems) litems[nl] = leaf_item_at(k, begin[i], count[i], chunk_rows, leaf_pos, i, 0);
+    leaf_pos += count[i] > 0 ? count[i] : 0;
+  }
+  const int64_t t[7] = {nh, nc, nl, zw + zc, n_zw, n_wide, n_general > 0};
+  std::memcpy(totals, t, sizeof(t));
+}
+
 int64_t tmog_abi_sizeof(int which) {
   const int64_t sizes[] = {sizeof(GrowArgs), sizeof(ResidentIO), sizeof(HistItem), sizeof(PartItem), sizeof(LeafItem)};
   return which >= 0 && which < 5 ? sizes[which] : -1;
