@@ -1007,12 +1007,27 @@ def _finalize_py(jobs, G: "_Nodes", mode, kind, K, S, missing_bin, with_gid_valu
 
 
 _PM_VK = N.ABI_CONSTS["TMOG_PM_VK"]      # tree_kernels.hip forest_predict_multi_kernel: variants x classes per model
+_PM_DEPTHS = 32                          # ... and its s_dmask: per-depth stop masks for depths 0.._PM_DEPTHS
 
 
 def _pm_lds_bytes(F: int) -> int:
     """LDS of one forest_predict_multi_kernel workgroup: 64 staged rows of F bins + 64 x 4 x 32 fp32
-    accumulators (tmog_hip_forest_predict_multi)."""
-    return ((64 * F + 15) & ~15) + 4 * _PM_VK * 64 * 4
+    accumulators (tmog_hip_forest_predict_multi) + the kernel's static depth table."""
+    return ((64 * F + 15) & ~15) + 4 * _PM_VK * 64 * 4 + 4 * (_PM_DEPTHS + 1)
+
+
+def _node_depth(f: Forest) -> np.ndarray:
+    """Depth of every node (roots 0), level by level over all trees at once."""
+    depth = np.zeros(len(f.nodes), np.int32)
+    frontier = f.tree_off[:-1].astype(np.int64)
+    frontier = frontier[frontier < f.tree_off[1:]]
+    d = 0
+    while frontier.size:
+        depth[frontier] = d
+        kids = f.nodes[frontier, 2:4].astype(np.int64)
+        frontier = kids[kids[:, 0] >= 0].ravel()
+        d += 1
+    return depth
 
 
 def _lds_limit(dev) -> int:
@@ -1059,15 +1074,21 @@ def forest_predict_multi(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[
             pos += counts[m] * K
     # per-node variant stop bits of the depth-independent part of prune_forest's rule: a grown leaf stops
     # every variant, an internal node those whose min gain exceeds its split gain (fp32 compare)
+    # The kernel's depth table ends at _PM_DEPTHS: a deeper max depth is folded into the node bits here (a tree
+    # deeper than that variant would otherwise be walked to its grown leaves)
     mask = np.zeros(len(forest.nodes), np.uint32)
     leaf = forest.nodes[:, 2] < 0
+    depth = _node_depth(forest) if any(d > _PM_DEPTHS for vs in model_variants for d, _ in vs) else None
     for m, vs in enumerate(model_variants):
         sel = np.zeros(len(forest.nodes), bool)
         for t in model_trees[m]:
             sel[int(forest.tree_off[t]):int(forest.tree_off[t + 1])] = True
         bits = np.zeros(len(forest.nodes), np.uint32)
-        for k, (_, g) in enumerate(vs):
-            bits |= ((forest.gain < np.float32(g)) | leaf).astype(np.uint32) << np.uint32(k)
+        for k, (d, g) in enumerate(vs):
+            stop = (forest.gain < np.float32(g)) | leaf
+            if d > _PM_DEPTHS:
+                stop |= depth >= d
+            bits |= stop.astype(np.uint32) << np.uint32(k)
         mask[sel] = bits[sel]
     pk = _Pack(dev)
     ids = [pk.add(forest.tree_off[:-1][order].astype(np.int64)), pk.add(np.ones(len(order), np.float32)),

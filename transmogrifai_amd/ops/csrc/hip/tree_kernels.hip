@@ -1663,7 +1663,9 @@ __global__ void __launch_bounds__(PM_ROWS * PM_TPR) forest_predict_multi_kernel(
   __syncthreads();
   // per-thread accumulators live in the LDS reduction area (dynamic variant index, no register arrays)
   // depth stop masks: s_dmask[d] = variants whose max depth is <= d (the gain / grown-leaf part of the
-  // rule is precomputed per node by the host: node_mask[k] = variants that stop at node k regardless of depth)
+  // rule is precomputed per node by the host: node_mask[k] = variants that stop at node k regardless of depth).
+  // The table ends at depth 32: a variant with var_depth > 32 is in no s_dmask entry, so for such a variant the
+  // host also sets its node_mask bit at every node of depth >= var_depth (tree_engine.forest_predict_multi).
   __shared__ uint32_t s_dmask[33];
   if (threadIdx.x < 33) {
     uint32_t mk = 0u;
@@ -2051,7 +2053,7 @@ int tmog_hip_forest_predict_multi(const uint8_t* Xb, int F, int n_models, const 
   if (n_models == 0 || max_rows == 0) return 0;
   if (K != 1 && K != 2 && K != 4 && K != 8) return -2;
   const size_t lds = (((size_t)PM_ROWS * F + 15) & ~(size_t)15) + sizeof(float) * PM_VK * PM_ROWS * PM_TPR;
-  if (lds > 160 * 1024) return -3;
+  if (lds + sizeof(uint32_t) * 33 > 160 * 1024) return -3;   // dynamic LDS + the kernel's static s_dmask[33]
   dim3 g2((unsigned)((max_rows + PM_ROWS - 1) / PM_ROWS), n_models);
 #define TM_PM(KV)                                                                                               \
   hipLaunchKernelGGL(forest_predict_multi_kernel<KV>, g2, dim3(PM_ROWS * PM_TPR), lds, stream, Xb, F,           \
