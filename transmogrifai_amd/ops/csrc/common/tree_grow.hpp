@@ -96,6 +96,23 @@ inline int fp_delay_ms(int rank, int group) {
 
 using ::GrowArgs;   // common/tmog_abi.h
 
+// Diagnostic switches of the level loops, each with one reader: the host-planned loop and the device-planned
+// loop's support check (hip/tree_resident.hip unsupported()) cannot disagree. Read per call: tests toggle
+// them within a process.
+inline bool env_is(const char* name, char c) {
+  const char* e = std::getenv(name);
+  return e && e[0] == c;
+}
+inline bool pair_scan_enabled() { return !env_is("TMOG_PAIR_SCAN", '0'); }
+inline bool fused_reduce_enabled() { return !env_is("TMOG_FUSED_REDUCE", '0'); }
+// (the launcher in hip/tree_kernels.hip that acts on this one keeps its own once-per-process read)
+inline bool hist_wide_split() { return env_is("TMOG_HIST_WIDE_SPLIT", '1'); }
+// Newton growth gates a split on the children's hessian sums: (g, h) statistics, second-order gain.
+// TMOG_TREE_HESS_GATE=0: off (A/B and the equality test).
+inline bool hess_gate(const GrowArgs& a) {
+  return a.mode == 2 && a.kind == 3 && a.S >= 2 && !env_is("TMOG_TREE_HESS_GATE", '0');
+}
+
 // Merge of the ranks' records of node j (host twin of tree_kernels.hip fp_merge_kernel).
 inline void fp_merge_host(const uint8_t* recv, int R, int m, size_t rb, int S, int32_t* feat, int32_t* bin,
                           float* gain, uint8_t* dl, float* left) {
@@ -362,9 +379,7 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
   if (n_sc > 256) throw std::runtime_error("too many statistic chunks (classes x bins too large)");
   const int fp_mlo = fp ? a.fp_mlo : 0;
   const size_t fp_rb = fp_rec_bytes(S);
-  const char* hg_env = std::getenv("TMOG_TREE_HESS_GATE");     // "0": off (A/B and the equality test)
-  const bool newton = a.mode == 2 && a.kind == 3 && S >= 2 &&   // (g, h) statistics, second-order gain
-                      !(hg_env && hg_env[0] == '0');
+  const bool newton = hess_gate(a);
   static const bool timing = std::getenv("TMOG_GROW_TIMING") != nullptr;
   using tclock = std::chrono::steady_clock;
   auto ns_since = [](tclock::time_point t) {
@@ -444,9 +459,7 @@ void grow_group(BK& bk, const GrowArgs& a, int g, GroupResult& R, FpTurns* turns
     }
     // GPU: a sibling pair's subtraction and both children's split scans run as one pass (pair_scan_kernel)
     // -- the two nodes are flagged (paired slot) so the node-wise scan skips them; same decisions
-    const char* ps_env = std::getenv("TMOG_PAIR_SCAN");
-    const bool pair_fuse = BK::kGPU && !use_subset && S <= 16 && B <= 64 && !d_big.empty() &&
-                           !(ps_env && ps_env[0] == '0');
+    const bool pair_fuse = BK::kGPU && !use_subset && S <= 16 && B <= 64 && !d_big.empty() && pair_scan_enabled();
     std::vector<int32_t> d_sj, d_bj;
     if (pair_fuse)
       for (size_t q = 0; q < d_big.size(); ++q) {

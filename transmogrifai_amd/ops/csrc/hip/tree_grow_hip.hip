@@ -22,39 +22,26 @@
 
 namespace {
 
-inline void hchk(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-inline void kchk(int rc, const char* what) {
-  if (rc != 0) throw std::runtime_error(std::string("kernel ") + what + " failed with code " + std::to_string(rc));
-}
+using tmog::hchk;
+using tmog::kchk;
 
-// per-(group slot) persistent resources: stream, pinned staging slots, device staging, result mirror
+// per-(group slot) persistent resources (hip/dev_alloc.hpp): stream, staged level arrays, result mirror, scratch
 struct GpuSlot {
   hipStream_t stream = nullptr;
   hipStream_t ext = nullptr;                 // caller-provided stream for this slot (tmog_hip_slot_stream)
   bool ext_set = false;
-  uint8_t* pin[3] = {nullptr, nullptr, nullptr};
-  size_t pin_cap[3] = {0, 0, 0};
-  uint8_t* dev[3] = {nullptr, nullptr, nullptr};
-  size_t dev_cap[3] = {0, 0, 0};
-  hipEvent_t copied[3] = {nullptr, nullptr, nullptr};   // last H2D copy out of pin[k]
-  uint8_t* res_dev = nullptr;
-  size_t res_cap = 0;
-  uint8_t* res_pin = nullptr;
-  size_t res_pin_cap = 0;
-  uint8_t* cand = nullptr;
-  size_t cand_cap = 0;
-  unsigned* done = nullptr;                  // per-node ticket counters of the fused split reduction (zeroed)
-  size_t done_cap = 0;
-  int32_t* feats = nullptr;
-  int feats_n = 0;
-  uint8_t* fp_send = nullptr;                 // feature-parallel: this rank's split records
-  size_t fp_send_cap = 0;
-  uint8_t* fp_recv = nullptr;                 // feature-parallel: all-gathered split records
-  size_t fp_recv_cap = 0;
-  uint8_t* hist[2] = {nullptr, nullptr};     // grow-only level histogram buffers (int64 words)
-  size_t hist_cap[2] = {0, 0};
+  tmog::StagedCopy stage[3];                 // level arrays, scatter items, leaf items
+  tmog::DevBuf res_dev;
+  tmog::PinBuf res_pin;
+  tmog::DevBuf cand;
+  tmog::Tickets done;
+  tmog::DevBuf feats;
+  int feats_n = 0;                           // features written to `feats` (0 .. feats_n - 1)
+  // Feature-parallel split records, this rank's and the all-gathered ones. Plain blocks here, stream-ordered
+  // ones in the device-planned loop (tree_resident.hip ResSlot): the two loops differ, and neither has run at
+  // world > 1 on hardware.
+  tmog::RawBuf fp_send, fp_recv;
+  tmog::DevBuf hist[2];                      // level histogram buffers (int64 words)
   int device = -1;
 };
 
@@ -75,69 +62,40 @@ struct GpuBackend {
   int group;
   GpuBackend(GpuSlot& s, const tmog::GrowArgs& args, int g) : sl(s), a(args), group(g) {}
 
-  // grow-only device buffers: dev_alloc.hpp (a failed growth leaves the buffer empty, never a stale capacity)
-  static void grow_dev(uint8_t*& p, size_t& cap, size_t need, hipStream_t s) {
-    tmog::grow_device(p, cap, need, need + need / 2 + 4096, s);
-  }
-  static void grow_pin(uint8_t*& p, size_t& cap, size_t need, hipStream_t s) {
-    if (need <= cap && p != nullptr) return;
-    if (p) {
-      hchk(hipStreamSynchronize(s), "sync before pinned realloc");
-      hipError_t e = hipHostFree(p);
-      p = nullptr;
-      cap = 0;
-      hchk(e, "hipHostFree");
-    }
-    const size_t nc = need + need / 2 + 4096;
-    hchk(hipHostMalloc((void**)&p, nc, hipHostMallocDefault), "hipHostMalloc");
-    cap = nc;
+  static size_t slack(size_t need) { return need + need / 2 + 4096; }   // this loop's growth policy
+  template <class Buf>
+  uint8_t* grown(Buf& b, size_t bytes) {
+    b.need(bytes, slack(bytes), sl.stream);
+    return b.as();
   }
   const int32_t* all_features(int F) {
     if (sl.feats_n < F) {
-      uint8_t* p = reinterpret_cast<uint8_t*>(sl.feats);
-      size_t cap = sl.feats ? sizeof(int32_t) * (size_t)sl.feats_n : 0;
-      sl.feats = nullptr;
       sl.feats_n = 0;
-      tmog::grow_device(p, cap, sizeof(int32_t) * (size_t)F, sizeof(int32_t) * (size_t)F, sl.stream);
+      const size_t bytes = sizeof(int32_t) * (size_t)F;
+      sl.feats.need(bytes, bytes, sl.stream);
       std::vector<int32_t> h(F);
       for (int i = 0; i < F; ++i) h[i] = i;
-      hchk(hipMemcpyAsync(p, h.data(), sizeof(int32_t) * F, hipMemcpyHostToDevice, sl.stream), "copy feats");
+      hchk(hipMemcpyAsync(sl.feats.as(), h.data(), bytes, hipMemcpyHostToDevice, sl.stream), "copy feats");
       hchk(hipStreamSynchronize(sl.stream), "sync feats");
-      sl.feats = reinterpret_cast<int32_t*>(p);
       sl.feats_n = F;
     }
-    return sl.feats;
+    return sl.feats.as<int32_t>();
   }
   // Staged host arrays -> device in one async copy. The pinned buffer is rewritten only after its
   // previous copy has completed: a level's leaf items (slot 2) can be shipped twice with no blocking
   // result read in between (leaves after the split read, then every node at the next level when
   // none of them can split), so the wait is explicit instead of relying on the level's fetch.
   const uint8_t* ship(const tmog::Staging& st, int k) {
-    const size_t n = st.buf.size() ? st.buf.size() : 16;
-    if (sl.copied[k]) hchk(hipEventSynchronize(sl.copied[k]), "stage copy wait");
-    else hchk(hipEventCreateWithFlags(&sl.copied[k], hipEventDisableTiming), "event create");
-    grow_pin(sl.pin[k], sl.pin_cap[k], n, sl.stream);
-    grow_dev(sl.dev[k], sl.dev_cap[k], n, sl.stream);
-    if (st.buf.size()) {
-      std::memcpy(sl.pin[k], st.buf.data(), st.buf.size());
-      hchk(hipMemcpyAsync(sl.dev[k], sl.pin[k], st.buf.size(), hipMemcpyHostToDevice, sl.stream), "stage copy");
-      hchk(hipEventRecord(sl.copied[k], sl.stream), "event record");
-    }
-    return sl.dev[k];
+    const size_t cap = slack(st.buf.size() ? st.buf.size() : 16);
+    return sl.stage[k].ship(st.buf.data(), st.buf.size(), cap, cap, sl.stream);
   }
-  int64_t* hist_buffer(int k, size_t words) {
-    grow_dev(sl.hist[k], sl.hist_cap[k], words * sizeof(int64_t), sl.stream);
-    return (int64_t*)sl.hist[k];
-  }
-  uint8_t* result_buffer(size_t bytes) {
-    grow_dev(sl.res_dev, sl.res_cap, bytes, sl.stream);
-    return sl.res_dev;
-  }
+  int64_t* hist_buffer(int k, size_t words) { return (int64_t*)grown(sl.hist[k], words * sizeof(int64_t)); }
+  uint8_t* result_buffer(size_t bytes) { return grown(sl.res_dev, bytes); }
   const uint8_t* fetch(const uint8_t* dev, size_t bytes) {
-    grow_pin(sl.res_pin, sl.res_pin_cap, bytes, sl.stream);
-    hchk(hipMemcpyAsync(sl.res_pin, dev, bytes, hipMemcpyDeviceToHost, sl.stream), "result copy");
+    uint8_t* h = grown(sl.res_pin, bytes);
+    hchk(hipMemcpyAsync(h, dev, bytes, hipMemcpyDeviceToHost, sl.stream), "result copy");
     hchk(hipStreamSynchronize(sl.stream), "result sync");
-    return sl.res_pin;
+    return h;
   }
   void zero_segments(int64_t* hist, const int64_t* off, const int64_t* size, int n, int64_t mx, int64_t dense, int per,
                      int S, int n_dense) {
@@ -169,64 +127,35 @@ struct GpuBackend {
   void pair_scan(const tmog::GrowArgs& g, int64_t* hist, const int64_t* prev, const int64_t* poff, const int32_t* sj,
                  const int32_t* bj, int n_pairs, const int64_t* nho, const int32_t* nnf, const int32_t* nfo,
                  const int32_t* flist, const float* params, const int32_t* nmd, int max_nf, int m, int n_multi) {
-    grow_dev(sl.cand, sl.cand_cap, tmog_hip_split_cand_bytes(m, max_nf, g.B, g.S), sl.stream);
+    uint8_t* cand = grown(sl.cand, tmog_hip_split_cand_bytes(m, max_nf, g.B, g.S));
     kchk(tmog_hip_pair_scan(hist, prev, poff, sj, bj, n_pairs, nho, nnf, nfo, flist, g.n_bins, g.B, g.S, g.kind, params,
-                            g.missing_bin, nmd, g.qinv, max_nf, sl.cand, n_multi, sl.stream, nullptr),
+                            g.missing_bin, nmd, g.qinv, max_nf, cand, n_multi, sl.stream, nullptr),
          "pair_scan");
   }
   void split_find(const tmog::GrowArgs& g, const int64_t* hist, int m, const int64_t* nho, const int32_t* nnf,
                   const int32_t* nfo, const int32_t* flist, const float* params, const int32_t* nmd, int max_nf,
                   int32_t* feat, int32_t* bin, float* gain, uint8_t* dl, float* left, float* tot, int64_t* cursors,
                   int n_multi, const tmog::FpSlice& fps) {
-    grow_dev(sl.cand, sl.cand_cap, tmog_hip_split_cand_bytes(m, max_nf, g.B, g.S), sl.stream);
-    const char* fr_env = std::getenv("TMOG_FUSED_REDUCE");      // read per call: A/B within one process
-    const bool fused_reduce = !(fr_env && fr_env[0] == '0');
-    if (fused_reduce && sl.done_cap < (size_t)m) {     // grow-only, zeroed; the kernels leave it zeroed
-      uint8_t* p = reinterpret_cast<uint8_t*>(sl.done);
-      size_t cap = sl.done_cap * sizeof(unsigned);
-      sl.done = nullptr;
-      sl.done_cap = 0;
-      const size_t n = (size_t)m + m / 2 + 256;
-      tmog::grow_device(p, cap, (size_t)m * sizeof(unsigned), n * sizeof(unsigned), sl.stream);
-      hchk(hipMemsetAsync(p, 0, n * sizeof(unsigned), sl.stream), "memset done");
-      sl.done = reinterpret_cast<unsigned*>(p);
-      sl.done_cap = n;
-    }
+    uint8_t* cand = grown(sl.cand, tmog_hip_split_cand_bytes(m, max_nf, g.B, g.S));
+    unsigned* done = nullptr;
+    if (tmog::fused_reduce_enabled())
+      done = sl.done.need((size_t)m, ((size_t)m + m / 2 + 256) * sizeof(unsigned), sl.stream);
     kchk(tmog_hip_split_find(hist, m, nho, nnf, nfo, flist, g.n_bins, g.B, g.S, g.kind, params, g.missing_bin, nmd,
-                             g.qinv, max_nf, sl.cand, feat, bin, gain, dl, left, tot, cursors, n_multi, fps.rec,
-                             fps.rec_bytes, fps.mlo, fps.nml, fps.obase, sl.stream, fused_reduce ? sl.done : nullptr,
-                             nullptr),
+                             g.qinv, max_nf, cand, feat, bin, gain, dl, left, tot, cursors, n_multi, fps.rec,
+                             fps.rec_bytes, fps.mlo, fps.nml, fps.obase, sl.stream, done, nullptr),
          "split_find");
   }
-  // RCCL send / receive buffers come from plain hipMalloc (grow-only; never from the stream-ordered
-  // pool of grow_dev): the collective library inspects and may register the buffers it is given.
-  static void grow_plain(uint8_t*& p, size_t& cap, size_t need, hipStream_t s) {
-    if (need <= cap && p != nullptr) return;
-    if (p) {
-      hchk(hipStreamSynchronize(s), "sync before rccl buffer realloc");
-      hipError_t e = hipFree(p);
-      p = nullptr;
-      cap = 0;
-      hchk(e, "hipFree");
-    }
-    const size_t nc = need + need / 2 + 4096;
-    hchk(hipMalloc((void**)&p, nc), "hipMalloc");
-    cap = nc;
-  }
-  uint8_t* fp_send_buffer(size_t bytes) {
-    grow_plain(sl.fp_send, sl.fp_send_cap, bytes, sl.stream);
-    return sl.fp_send;
-  }
+  uint8_t* fp_send_buffer(size_t bytes) { return grown(sl.fp_send, bytes); }
   // One RCCL all-gather of the level's split records over xGMI (this group's communicator, on the
   // group's stream: no host round trip), then the merge kernel rewrites the decisions in place.
   void fp_exchange_merge(const tmog::GrowArgs& g, const uint8_t* rec, int m, size_t rb, int32_t* feat, int32_t* bin,
                          float* gain, uint8_t* dl, float* left) {
     const size_t bytes = rb * (size_t)m;
-    grow_plain(sl.fp_recv, sl.fp_recv_cap, bytes * (size_t)g.fp_world, sl.stream);
+    uint8_t* recv = grown(sl.fp_recv, bytes * (size_t)g.fp_world);
     ncclComm_t comm = (ncclComm_t)g.fp_comm[group];
     if (comm == nullptr) {        // single-GPU projection of a rank group: the exchange answered locally
       for (int r = 0; r < g.fp_world; ++r)
-        hchk(hipMemcpyAsync(sl.fp_recv + (size_t)r * bytes, rec, bytes, hipMemcpyDeviceToDevice, sl.stream),
+        hchk(hipMemcpyAsync(recv + (size_t)r * bytes, rec, bytes, hipMemcpyDeviceToDevice, sl.stream),
              "fp local exchange");
     } else {
       ncclResult_t r;
@@ -234,11 +163,11 @@ struct GpuBackend {
         // enqueue under a process-wide lock: the job groups' host threads issue their (independent,
         // per-communicator) collectives concurrently, and RCCL's enqueue path keeps process-global state
         std::lock_guard<std::mutex> lk(rccl_mutex());
-        r = ncclAllGather(rec, sl.fp_recv, bytes, ncclUint8, comm, sl.stream);
+        r = ncclAllGather(rec, recv, bytes, ncclUint8, comm, sl.stream);
       }
       if (r != ncclSuccess) throw std::runtime_error(std::string("ncclAllGather: ") + ncclGetErrorString(r));
     }
-    kchk(tmog_hip_fp_merge(sl.fp_recv, g.fp_world, m, (int64_t)rb, g.S, feat, bin, gain, dl, left, sl.stream),
+    kchk(tmog_hip_fp_merge(recv, g.fp_world, m, (int64_t)rb, g.S, feat, bin, gain, dl, left, sl.stream),
          "fp_merge");
   }
   void partition_fused(const tmog::GrowArgs& g, const uint32_t* rows, uint32_t* rows_alt, const void* items, int n,

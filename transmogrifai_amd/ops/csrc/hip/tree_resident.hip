@@ -650,32 +650,24 @@ __global__ void __launch_bounds__(1024) tree_finalize_kernel(FinArgs A) {
   }
 }
 
-inline void hchk(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-inline void kchk(int rc, const char* what) {
-  if (rc != 0) throw std::runtime_error(std::string("kernel ") + what + " failed with code " + std::to_string(rc));
-}
+using tmog::hchk;
+using tmog::kchk;
 
-// Per-slot device resources of the resident grower (grow-only; stream-ordered allocations on the caller's
-// stream, which every use of the slot is ordered on).
-struct Buf {
-  uint8_t* p = nullptr;
-  size_t cap = 0;
-  void need(size_t bytes, hipStream_t s) {     // dev_alloc.hpp: a failed growth leaves the buffer empty
-    tmog::grow_device(p, cap, bytes, bytes + bytes / 4 + 4096, s);
-  }
-};
-
+// Per-slot device resources of the resident grower (hip/dev_alloc.hpp; stream-ordered allocations on the
+// caller's stream, which every use of the slot is ordered on).
 struct ResSlot {
-  Buf arena, hist0, hist1, cand, done, res, consts, fp_send, fp_recv;
-  uint8_t* pin = nullptr;      // pinned staging of the per-call constants
-  size_t pin_cap = 0;
-  hipEvent_t copied = nullptr;
+  tmog::DevBuf arena, hist[2], cand;
+  tmog::Tickets done;
+  // Feature-parallel split records, this rank's and the all-gathered ones. Stream-ordered blocks here, plain
+  // hipMalloc ones in the host-planned loop (tree_grow_hip.hip GpuSlot): the two loops differ, and neither has
+  // run at world > 1 on hardware.
+  tmog::DevBuf fp_send, fp_recv;
+  tmog::StagedCopy consts;     // the per-call constants
   std::vector<uint8_t> last;   // constants last shipped (skipped when unchanged)
-  const uint8_t* done_zeroed = nullptr;   // the ticket-counter block last zeroed (a new block is zeroed again)
   int device = -1;
 };
+
+inline size_t slack(size_t bytes) { return bytes + bytes / 4 + 4096; }   // this loop's growth policy
 
 std::vector<ResSlot>& res_slots() {
   static std::vector<ResSlot> s(32);
@@ -746,14 +738,310 @@ std::string unsupported(const tmog::GrowArgs& a) {
     const int k = a.job_fsub[j];
     if (k > 0 && k < a.F) return "per-node feature subsets";
   }
-  const char* ps = std::getenv("TMOG_PAIR_SCAN");
-  if (ps && ps[0] == '0') return "pair scan disabled";
-  const char* fr = std::getenv("TMOG_FUSED_REDUCE");
-  if (fr && fr[0] == '0') return "fused reduction disabled";
-  const char* ws = std::getenv("TMOG_HIST_WIDE_SPLIT");
-  if (ws && ws[0] == '1') return "split wide-load launches";
+  if (!tmog::pair_scan_enabled()) return "pair scan disabled";
+  if (!tmog::fused_reduce_enabled()) return "fused reduction disabled";
+  if (tmog::hist_wide_split()) return "split wide-load launches";
   if (tmog_hip_hist_stat_chunk(a.B, a.S) < a.S) return "chunked statistics";
   return "";
+}
+
+constexpr int kNsc = 1;   // statistic chunks per histogram item (unsupported(): one chunk holds all S)
+
+// ---- the steps of one call (tmog_hip_grow_resident), in the order they run
+
+// Everything carved out of the slot's arena: the planner's arrays (set in `plan`, whose other members
+// plan_args() fills), split_find's outputs (which the planner reads) and the finalisation's scratch (in `fin`).
+struct Arena {
+  PlanArgs plan{};
+  FinArgs fin{};
+  int32_t *r_feat, *r_bin;
+  float *r_gain, *r_left, *r_tot;
+  uint8_t* r_dl;
+  int64_t* r_cur;
+};
+
+// Called with a null base for the arena's size (cv.off afterwards), then with the real base.
+Arena lay_out(Carve& cv, const Caps& cp, int S) {
+  Arena A;
+  PlanArgs& P = A.plan;
+  for (int k = 0; k < 2; ++k) {
+    P.lv_tree[k] = cv.take<int32_t>(cp.cap_nl);
+    P.lv_gid[k] = cv.take<int32_t>(cp.cap_nl);
+    P.lv_begin[k] = cv.take<int64_t>(cp.cap_nl);
+    P.lv_count[k] = cv.take<int64_t>(cp.cap_nl);
+    P.hn[k] = cv.take<int32_t>(cp.cap_m);
+    P.nmd[k] = cv.take<int32_t>(cp.cap_m);
+    P.nho[k] = cv.take<int64_t>(cp.cap_m);
+    P.par[k] = cv.take<float>(8 * cp.cap_m);
+    P.nb[k] = cv.take<int64_t>(cp.cap_m);
+    P.nc[k] = cv.take<int64_t>(cp.cap_m);
+  }
+  P.nfo = cv.take<int32_t>(cp.cap_m);
+  P.nnf = cv.take<int32_t>(cp.cap_m);
+  P.sj = cv.take<int32_t>(cp.cap_m);
+  P.bj = cv.take<int32_t>(cp.cap_m);
+  P.poff = cv.take<int64_t>(cp.cap_m);
+  P.zoff = cv.take<int64_t>(cp.cap_m);
+  P.zsize = cv.take<int64_t>(cp.cap_m);
+  P.ppo = cv.take<int64_t>(cp.cap_nl);
+  P.hitems = cv.take<HistItemH>(cp.cap_h);
+  P.citems = cv.take<PartItemH>(cp.cap_c);
+  P.litems = cv.take<LeafItemH>(cp.cap_l);
+  P.sa = cv.take<int64_t>(cp.cap_nl);
+  P.sb = cv.take<int64_t>(cp.cap_nl);
+  P.sc = cv.take<int64_t>(cp.cap_nl);
+  P.sd = cv.take<int64_t>(cp.cap_nl);
+  P.se = cv.take<int64_t>(cp.cap_nl);
+  P.sf = cv.take<int64_t>(cp.cap_nl);
+  P.sg = cv.take<int64_t>(cp.cap_nl);
+  P.flag = cv.take<int32_t>(cp.cap_nl);
+  P.loc = cv.take<int32_t>(cp.cap_nl);
+  P.cnt = cv.take<int>(C_COUNT);
+  P.leaf_pos = cv.take<int64_t>(1);
+  P.level_off = cv.take<int32_t>(cp.D + 2);
+  P.r_feat = A.r_feat = cv.take<int32_t>(cp.cap_m);
+  P.r_bin = A.r_bin = cv.take<int32_t>(cp.cap_m);
+  P.r_gain = A.r_gain = cv.take<float>(cp.cap_m);
+  P.r_left = A.r_left = cv.take<float>((int64_t)S * cp.cap_m);
+  P.r_tot = A.r_tot = cv.take<float>((int64_t)S * cp.cap_m);
+  P.r_dl = A.r_dl = cv.take<uint8_t>(cp.cap_m);
+  P.r_cur = A.r_cur = cv.take<int64_t>(2 * cp.cap_m);
+  A.fin.left_w = cv.take<int64_t>(cp.cap_nodes);
+  A.fin.right_w = cv.take<int64_t>(cp.cap_nodes);
+  A.fin.parent = cv.take<int64_t>(cp.cap_nodes);
+  A.fin.reach = cv.take<int32_t>(cp.cap_nodes);
+  A.fin.value = cv.take<double>(cp.cap_nodes);
+  return A;
+}
+
+// The per-call constants on the device: the block and the byte offset of each array in it.
+struct Consts {
+  const uint8_t* dev;
+  size_t groups, flist, depth, model, count, inst, gain, mcw, lam, eps, eta, gamma;
+  template <class T>
+  const T* at(size_t off) const { return reinterpret_cast<const T*>(dev + off); }
+};
+
+// What the steps of one call share.
+struct Ctx {
+  const tmog::GrowArgs& a;
+  const ResidentIO& io;
+  ResSlot& sl;
+  hipStream_t st;
+  tmog::GroupLayout L;
+  Caps cp;
+  int64_t hsz;                 // histogram words per node
+  bool need_general;           // any item on the byte-gather path: that of a built node
+  Consts K;
+  Arena A;
+  PlanArgs plan;
+  int64_t* hist[2];            // reserve()
+  uint8_t* cand;
+  unsigned* done;
+  uint8_t *fp_send, *fp_recv;  // feature-parallel only, else null
+};
+
+// Feature groups, feature list and job table, shipped only when they differ from the last shipped block.
+Consts ship_constants(Ctx& c) {
+  const tmog::GrowArgs& a = c.a;
+  const size_t T = (size_t)a.T;
+  std::vector<int32_t> flist(c.L.F_use);
+  for (int f = 0; f < c.L.F_use; ++f) flist[f] = c.L.perm_feats.empty() ? f : c.L.perm_feats[f];
+  tmog::Staging cs;
+  Consts K{nullptr,   // (braced initialisers are evaluated in order: the offsets are those of the members)
+           cs.add(c.L.full_groups), cs.add(flist),
+           cs.add(a.job_depth, 4 * T), cs.add(a.job_model, 4 * T),
+           cs.add(a.job_count, 8 * T), cs.add(a.job_min_inst, 8 * T),
+           cs.add(a.job_min_gain, 8 * T), cs.add(a.job_mcw, 8 * T),
+           cs.add(a.job_lambda, 8 * T), cs.add(a.job_eps, 8 * T),
+           cs.add(c.io.job_eta, 8 * T), cs.add(c.io.job_gamma, 8 * T)};
+  const size_t n = cs.buf.size();
+  if (c.sl.consts.dev.need(n, slack(n), c.st)) c.sl.last.clear();   // a new block holds nothing yet
+  if (cs.buf != c.sl.last) {
+    c.sl.consts.ship(cs.buf.data(), n, n + 4096, slack(n), c.st);
+    c.sl.last = cs.buf;
+  }
+  K.dev = c.sl.consts.dev.as();
+  return K;
+}
+
+// Histograms of two levels, split candidates, ticket counters; feature-parallel: the split records of this rank
+// and of every rank of the group.
+void reserve(Ctx& c) {
+  ResSlot& sl = c.sl;
+  auto grown = [&](tmog::DevBuf& b, size_t bytes) {
+    b.need(bytes, slack(bytes), c.st);
+    return b.as();
+  };
+  const size_t m = (size_t)c.cp.cap_m;
+  for (int k = 0; k < 2; ++k) c.hist[k] = (int64_t*)grown(sl.hist[k], sizeof(int64_t) * (size_t)c.hsz * m);
+  c.cand = grown(sl.cand, tmog_hip_split_cand_bytes((int)m, c.L.F_use, c.a.B, c.a.S));
+  c.done = sl.done.need(m, slack(sizeof(unsigned) * m), c.st);
+  const bool fp = c.a.fp_world > 0;
+  const size_t rec = tmog::fp_rec_bytes(c.a.S) * m;
+  c.fp_send = fp ? grown(sl.fp_send, rec) : nullptr;
+  c.fp_recv = fp ? grown(sl.fp_recv, rec * (size_t)c.a.fp_world) : nullptr;
+}
+
+// TMOG_PLAN_PROFILE, TMOG_PLAN_LDS, TMOG_PLAN_THREADS and the planner's LDS attribute: once per process.
+struct PlanLaunch {
+  bool profile;
+  bool lds;      // planner scratch in LDS when the per-level node capacity fits (TMOG_PLAN_LDS=0: global memory)
+  int threads;   // of the two single-workgroup kernels (plan, finalisation); TMOG_PLAN_THREADS = 256 / 512 / 1024:
+                 // a smaller workgroup finds a CU sooner while the other boosting parts' histogram waves occupy the chip
+};
+constexpr size_t kPlanLdsMax = 148 * 1024;
+
+const PlanLaunch& plan_launch_config() {
+  static const PlanLaunch cfg = [] {
+    const char* e = std::getenv("TMOG_PLAN_THREADS");
+    const int v = e ? std::atoi(e) : 1024;
+    const bool attr = hipFuncSetAttribute((const void*)level_plan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)kPlanLdsMax) == hipSuccess;
+    return PlanLaunch{tmog::env_is("TMOG_PLAN_PROFILE", '1'), attr && !tmog::env_is("TMOG_PLAN_LDS", '0'),
+                      (v == 256 || v == 512) ? v : 1024};
+  }();   // (thread-safe static initialisation)
+  return cfg;
+}
+
+inline size_t plan_lds_bytes(int64_t cap_nl) {
+  return ((size_t)kPlanScratch * sizeof(int64_t) + sizeof(int32_t)) * (size_t)cap_nl + 64;
+}
+
+PlanArgs plan_args(const Ctx& c) {
+  const tmog::GrowArgs& a = c.a;
+  const Caps& cp = c.cp;
+  const Consts& K = c.K;
+  PlanArgs P = c.A.plan;
+  P.T = a.T;
+  P.S = a.S;
+  P.chunk_rows = (int)a.chunk_rows;
+  P.n_groups = (int)c.L.full_groups.size();
+  P.n_sc = kNsc;
+  P.newton = tmog::hess_gate(a) ? 1 : 0;
+  P.subtract = 1;
+  P.pair_fuse = 1;
+  P.F_use = c.L.F_use;
+  P.has_missing = a.missing_bin >= 0 ? 1 : 0;
+  P.hsz = c.hsz;
+  P.live_dense = c.L.live_dense;
+  P.groups = K.at<tmog::FeatGroup>(K.groups);
+  P.j_depth = K.at<int32_t>(K.depth);
+  P.j_model = K.at<int32_t>(K.model);
+  P.j_count = K.at<int64_t>(K.count);
+  P.j_inst = K.at<double>(K.inst);
+  P.j_gain = K.at<double>(K.gain);
+  P.j_mcw = K.at<double>(K.mcw);
+  P.j_lam = K.at<double>(K.lam);
+  P.j_eps = K.at<double>(K.eps);
+  P.rec = c.io.rec;
+  P.W = kRecFixed + a.S;
+  P.cap_nl = cp.cap_nl;
+  P.cap_m = cp.cap_m;
+  P.cap_nodes = cp.cap_nodes;
+  P.cap_h = cp.cap_h;
+  P.cap_c = cp.cap_c;
+  P.cap_l = cp.cap_l;
+  const PlanLaunch& cfg = plan_launch_config();
+  P.profile = cfg.profile ? 1 : 0;
+  P.lds_cap = cfg.lds && cp.cap_nl > 0 && plan_lds_bytes(cp.cap_nl) <= kPlanLdsMax ? cp.cap_nl : 0;
+  return P;
+}
+
+FinArgs fin_args(const Ctx& c) {
+  FinArgs Fa = c.A.fin;
+  Fa.T = c.a.T;
+  Fa.S = c.a.S;
+  Fa.mode = c.a.mode;
+  Fa.kind = c.a.kind;
+  Fa.n_levels = c.cp.D + 1;
+  Fa.prune = 0;
+  for (int j = 0; j < c.a.T; ++j) Fa.prune |= c.io.job_gamma[j] > 0.0 ? 1 : 0;
+  Fa.rec = c.io.rec;
+  Fa.W = c.plan.W;
+  Fa.level_off = c.plan.level_off;
+  Fa.cnt = c.plan.cnt;
+  Fa.leaf_pos = c.plan.leaf_pos;
+  Fa.j_lam = c.plan.j_lam;
+  Fa.j_eta = c.K.at<double>(c.K.eta);
+  Fa.j_gamma = c.K.at<double>(c.K.gamma);
+  Fa.gid_value = c.io.gid_value;
+  Fa.gid_tree = c.io.gid_tree;
+  return Fa;
+}
+
+// Level d: plan -> leaf_collect -> zero -> hist_build -> pair_scan -> split_find -> [all-gather + merge] ->
+// partition. Every launch gets a host upper bound of its grid and reads the real count from c.plan.cnt.
+// Levels 0..D build histograms (level D only when D == 0: deeper, no node of level D may split); plan D + 1
+// only turns the last decisions into leaves.
+void enqueue_level(Ctx& c, int d) {
+  const tmog::GrowArgs& a = c.a;
+  const Caps& cp = c.cp;
+  const tmog::GroupLayout& L = c.L;
+  const Arena& A = c.A;
+  PlanArgs& P = c.plan;
+  hipStream_t st = c.st;
+  const int B = a.B, S = a.S, F_use = L.F_use, n_groups = (int)L.full_groups.size();
+  const int64_t total = cp.total;
+  int* cnt = P.cnt;
+  const int32_t* flist = c.K.at<int32_t>(c.K.flist);
+  uint32_t* const rows[2] = {a.rows, a.rows_alt};
+  int32_t* const gh[2] = {a.gh, a.gh_alt};
+  const bool use_gh = a.gh != nullptr && a.gh_alt != nullptr && a.mode == 2;
+  const bool fp = a.fp_world > 0;
+  const size_t fp_rb = tmog::fp_rec_bytes(S);
+
+  P.d = d;
+  hipLaunchKernelGGL(level_plan_kernel, dim3(1), dim3(plan_launch_config().threads),
+                     P.lds_cap > 0 ? plan_lds_bytes(P.lds_cap) : 0, st, P);
+  kchk((int)hipGetLastError(), "level_plan");
+  const int64_t nprev = d > 0 ? cp.nmax[d - 1] : 0;
+  const int64_t lbound = tmog::leaf_items_bound(a.chunk_rows, total, nprev) +
+                         tmog::leaf_items_bound(a.chunk_rows, total, cp.nmax[d]);
+  kchk(tmog_hip_leaf_collect(rows[0], P.litems, (int)std::min(lbound, cp.cap_l), a.leaf_rows, a.leaf_gid, st,
+                             rows[1], cnt + C_NL),
+       "leaf_collect");
+  if (d > cp.D || (d == cp.D && d > 0)) return;
+  const int k = d & 1;
+  const int64_t mb = cp.nmax[d];
+  kchk(tmog_hip_zero_segments(c.hist[k], P.zoff, P.zsize, (int)mb, c.hsz, L.live_dense, B * S, S, st, 0, cnt + C_NZ),
+       "zero_segments");
+  const int64_t hb = tmog::hist_items_bound(L.full_groups.data(), n_groups, a.chunk_rows, kNsc, total, mb);
+  kchk(tmog_hip_hist_build(a.Xb, a.F, rows[k], P.hitems, (int)std::min(hb, cp.cap_h), P.nfo, flist, P.nmd[k],
+                           P.nho[k], c.hist[k], B, a.mode, S, a.y, a.t1, a.t2, a.stride, a.qscale,
+                           a.mode == 2 ? a.missing_bin : -1, a.csr_ptr, a.csr_col, S, 0, c.need_general ? 1 : 0, st,
+                           use_gh ? gh[k] : nullptr, cnt + C_NH, a.wide_rows, a.Xh, a.Fh),
+       "hist_build");
+  if (d > 0)
+    kchk(tmog_hip_pair_scan(c.hist[k], c.hist[k ^ 1], P.poff, P.sj, P.bj, (int)std::max<int64_t>(1, mb / 2), P.nho[k],
+                            P.nnf, P.nfo, flist, a.n_bins, B, S, a.kind, P.par[k], a.missing_bin, P.nmd[k], a.qinv,
+                            F_use, c.cand, L.split_n_multi, st, cnt + C_NP),
+         "pair_scan");
+  kchk(tmog_hip_split_find(c.hist[k], (int)mb, P.nho[k], P.nnf, P.nfo, flist, a.n_bins, B, S, a.kind, P.par[k],
+                           a.missing_bin, P.nmd[k], a.qinv, F_use, c.cand, A.r_feat, A.r_bin, A.r_gain, A.r_dl,
+                           A.r_left, A.r_tot, A.r_cur, L.split_n_multi, c.fp_send, fp ? (int64_t)fp_rb : 0,
+                           fp ? a.fp_mlo : 0, fp ? L.fp_nml : 0, fp ? L.fp_obase : 0, st, c.done, cnt + C_M),
+       "split_find");
+  if (fp) {
+    // the ranks' best split per node: all-gather the level's records (the host bound mb of them; the
+    // merge reads the device count) and merge them into this level's decisions, all on the stream
+    kchk(tmog_hip_fp_allgather(c.fp_send, c.fp_recv, (int64_t)(fp_rb * (size_t)mb), a.fp_comm[0], a.fp_world, st),
+         "fp_allgather");
+    kchk(tmog_hip_fp_merge_dev(c.fp_recv, a.fp_world, (int)mb, (int64_t)fp_rb, S, A.r_feat, A.r_bin, A.r_gain,
+                               A.r_dl, A.r_left, cnt + C_M, st),
+         "fp_merge");
+  }
+  kchk(tmog_hip_partition_fused(a.Xb, a.F, rows[k], rows[k ^ 1], P.citems,
+                                (int)std::min(tmog::part_items_bound(total, mb), cp.cap_c), P.nb[k], P.nc[k],
+                                A.r_feat, A.r_bin, A.r_dl, P.par[k], A.r_gain, a.missing_bin, A.r_cur, a.XbT, a.N, st,
+                                use_gh ? gh[k] : nullptr, use_gh ? gh[k ^ 1] : nullptr, cnt + C_NC, a.wide_rows),
+       "partition_fused");
+}
+
+// Leaf values, gamma pruning and the created-node header, after the last level.
+void enqueue_finalize(const Ctx& c) {
+  hipLaunchKernelGGL(tree_finalize_kernel, dim3(1), dim3(plan_launch_config().threads), 0, c.st, fin_args(c));
+  kchk((int)hipGetLastError(), "tree_finalize");
 }
 
 }  // namespace
@@ -764,7 +1052,7 @@ int64_t tmog_hip_resident_cap_nodes(const tmog::GrowArgs* args) {
   const tmog::GrowArgs& a = *args;
   if (!unsupported(a).empty()) return -1;
   const tmog::GroupLayout L = tmog::group_layout<true>(a, false, a.fp_world > 0);
-  return caps_of(a, L, 1).cap_nodes;
+  return caps_of(a, L, kNsc).cap_nodes;
 }
 
 // TMOG_PLAN_PROFILE: copy the planner's per-phase tick sums (32 entries, 100 MHz wall clock; [31] = calls).
@@ -799,9 +1087,7 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
       g_err = why;
       return 1;
     }
-    const int T = a.T, S = a.S, B = a.B;
     if (a.slot_base < 0 || a.slot_base >= (int)res_slots().size()) throw std::runtime_error("bad slot");
-    hipStream_t st = (hipStream_t)a.stream;
     int dev = 0;
     hchk(hipGetDevice(&dev), "hipGetDevice");
     (void)tmog_hip_tree_prime();
@@ -810,268 +1096,22 @@ int tmog_hip_grow_resident(const tmog::GrowArgs* args, const ResidentIO* io) {
       sl = ResSlot();
       sl.device = dev;
     }
-    const bool fp = a.fp_world > 0;
-    const tmog::GroupLayout L = tmog::group_layout<true>(a, false, fp);
-    const int n_sc = 1;
-    const Caps cp = caps_of(a, L, n_sc);
-    if (io->cap_nodes < cp.cap_nodes) throw std::runtime_error("record buffer too small");
-    const int64_t total = cp.total;
-    const int F_use = L.F_use;
-    const int64_t hsz = (int64_t)F_use * B * S;
-    const int W = kRecFixed + S;
-    // ---- per-call constants: groups, feature list, job table (shipped only when they change)
-    const std::vector<tmog::FeatGroup>& groups = L.full_groups;
-    const int n_groups = (int)groups.size();
-    // any item on the byte-gather path: that of a built node
-    const bool need_general = tmog::node_work(tmog::kNodeNeed, 1, a.chunk_rows, groups.data(), n_groups, n_sc,
-                                              L.live_dense, hsz).n_general > 0;
-    std::vector<int32_t> flist(F_use);
-    for (int f = 0; f < F_use; ++f) flist[f] = L.perm_feats.empty() ? f : L.perm_feats[f];
-    tmog::Staging cs;
-    const size_t o_groups = cs.add(groups), o_flist = cs.add(flist);
-    const size_t o_depth = cs.add(a.job_depth, 4 * (size_t)T), o_model = cs.add(a.job_model, 4 * (size_t)T);
-    const size_t o_count = cs.add(a.job_count, 8 * (size_t)T), o_inst = cs.add(a.job_min_inst, 8 * (size_t)T);
-    const size_t o_gain = cs.add(a.job_min_gain, 8 * (size_t)T), o_mcw = cs.add(a.job_mcw, 8 * (size_t)T);
-    const size_t o_lam = cs.add(a.job_lambda, 8 * (size_t)T), o_eps = cs.add(a.job_eps, 8 * (size_t)T);
-    const size_t o_eta = cs.add(io->job_eta, 8 * (size_t)T), o_gam = cs.add(io->job_gamma, 8 * (size_t)T);
-    const uint8_t* consts_before = sl.consts.p;
-    sl.consts.need(cs.buf.size(), st);
-    if (sl.consts.p != consts_before) sl.last.clear();     // a new block holds nothing yet
-    if (cs.buf != sl.last) {
-      if (sl.copied) hchk(hipEventSynchronize(sl.copied), "constants copy wait");
-      else hchk(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming), "event");
-      if (sl.pin_cap < cs.buf.size() || sl.pin == nullptr) {
-        if (sl.pin) {
-          hipError_t e = hipHostFree(sl.pin);
-          sl.pin = nullptr;
-          sl.pin_cap = 0;
-          hchk(e, "hipHostFree");
-        }
-        hchk(hipHostMalloc((void**)&sl.pin, cs.buf.size() + 4096, hipHostMallocDefault), "hipHostMalloc");
-        sl.pin_cap = cs.buf.size() + 4096;
-      }
-      std::memcpy(sl.pin, cs.buf.data(), cs.buf.size());
-      hchk(hipMemcpyAsync(sl.consts.p, sl.pin, cs.buf.size(), hipMemcpyHostToDevice, st), "constants copy");
-      hchk(hipEventRecord(sl.copied, st), "event record");
-      sl.last = cs.buf;
-    }
-    const uint8_t* K = sl.consts.p;
-    // ---- arena
-    auto carve_all = [&](Carve& cv, PlanArgs& P, FinArgs& Fa, int** cnt, int64_t** leaf_pos, int32_t** level_off,
-                         int32_t** r_feat, int32_t** r_bin, float** r_gain, float** r_left, float** r_tot,
-                         uint8_t** r_dl, int64_t** r_cur) {
-      for (int k = 0; k < 2; ++k) {
-        P.lv_tree[k] = cv.take<int32_t>(cp.cap_nl);
-        P.lv_gid[k] = cv.take<int32_t>(cp.cap_nl);
-        P.lv_begin[k] = cv.take<int64_t>(cp.cap_nl);
-        P.lv_count[k] = cv.take<int64_t>(cp.cap_nl);
-        P.hn[k] = cv.take<int32_t>(cp.cap_m);
-        P.nmd[k] = cv.take<int32_t>(cp.cap_m);
-        P.nho[k] = cv.take<int64_t>(cp.cap_m);
-        P.par[k] = cv.take<float>(8 * cp.cap_m);
-        P.nb[k] = cv.take<int64_t>(cp.cap_m);
-        P.nc[k] = cv.take<int64_t>(cp.cap_m);
-      }
-      P.nfo = cv.take<int32_t>(cp.cap_m);
-      P.nnf = cv.take<int32_t>(cp.cap_m);
-      P.sj = cv.take<int32_t>(cp.cap_m);
-      P.bj = cv.take<int32_t>(cp.cap_m);
-      P.poff = cv.take<int64_t>(cp.cap_m);
-      P.zoff = cv.take<int64_t>(cp.cap_m);
-      P.zsize = cv.take<int64_t>(cp.cap_m);
-      P.ppo = cv.take<int64_t>(cp.cap_nl);
-      P.hitems = cv.take<HistItemH>(cp.cap_h);
-      P.citems = cv.take<PartItemH>(cp.cap_c);
-      P.litems = cv.take<LeafItemH>(cp.cap_l);
-      P.sa = cv.take<int64_t>(cp.cap_nl);
-      P.sb = cv.take<int64_t>(cp.cap_nl);
-      P.sc = cv.take<int64_t>(cp.cap_nl);
-      P.sd = cv.take<int64_t>(cp.cap_nl);
-      P.se = cv.take<int64_t>(cp.cap_nl);
-      P.sf = cv.take<int64_t>(cp.cap_nl);
-      P.sg = cv.take<int64_t>(cp.cap_nl);
-      P.flag = cv.take<int32_t>(cp.cap_nl);
-      P.loc = cv.take<int32_t>(cp.cap_nl);
-      *cnt = cv.take<int>(C_COUNT);
-      *leaf_pos = cv.take<int64_t>(1);
-      *level_off = cv.take<int32_t>(cp.D + 2);
-      *r_feat = cv.take<int32_t>(cp.cap_m);
-      *r_bin = cv.take<int32_t>(cp.cap_m);
-      *r_gain = cv.take<float>(cp.cap_m);
-      *r_left = cv.take<float>((int64_t)S * cp.cap_m);
-      *r_tot = cv.take<float>((int64_t)S * cp.cap_m);
-      *r_dl = cv.take<uint8_t>(cp.cap_m);
-      *r_cur = cv.take<int64_t>(2 * cp.cap_m);
-      Fa.left_w = cv.take<int64_t>(cp.cap_nodes);
-      Fa.right_w = cv.take<int64_t>(cp.cap_nodes);
-      Fa.parent = cv.take<int64_t>(cp.cap_nodes);
-      Fa.reach = cv.take<int32_t>(cp.cap_nodes);
-      Fa.value = cv.take<double>(cp.cap_nodes);
-    };
-    PlanArgs P{};
-    static const bool plan_prof = [] { const char* e = std::getenv("TMOG_PLAN_PROFILE"); return e && e[0] == '1'; }();
-    P.profile = plan_prof ? 1 : 0;
-    FinArgs Fa{};
-    int* cnt;
-    int64_t* leaf_pos;
-    int32_t* level_off;
-    int32_t *r_feat, *r_bin;
-    float *r_gain, *r_left, *r_tot;
-    uint8_t* r_dl;
-    int64_t* r_cur;
-    {
-      Carve probe{nullptr};
-      carve_all(probe, P, Fa, &cnt, &leaf_pos, &level_off, &r_feat, &r_bin, &r_gain, &r_left, &r_tot, &r_dl, &r_cur);
-      sl.arena.need(probe.off + 256, st);
-      Carve cv{sl.arena.p};
-      carve_all(cv, P, Fa, &cnt, &leaf_pos, &level_off, &r_feat, &r_bin, &r_gain, &r_left, &r_tot, &r_dl, &r_cur);
-    }
-    sl.hist0.need(sizeof(int64_t) * (size_t)hsz * cp.cap_m, st);
-    sl.hist1.need(sizeof(int64_t) * (size_t)hsz * cp.cap_m, st);
-    sl.cand.need(tmog_hip_split_cand_bytes((int)cp.cap_m, F_use, B, S), st);
-    sl.done.need(sizeof(unsigned) * (size_t)cp.cap_m, st);
-    const size_t fp_rb = tmog::fp_rec_bytes(S);
-    if (fp) {                                  // split records of this rank / of every rank of the group
-      sl.fp_send.need(fp_rb * (size_t)cp.cap_m, st);
-      sl.fp_recv.need(fp_rb * (size_t)cp.cap_m * (size_t)a.fp_world, st);
-    }
-    if (sl.done_zeroed != sl.done.p) {       // ticket counters start (and are left) at zero
-      hchk(hipMemsetAsync(sl.done.p, 0, sl.done.cap, st), "memset done");
-      sl.done_zeroed = sl.done.p;
-    }
-    int64_t* hist[2] = {(int64_t*)sl.hist0.p, (int64_t*)sl.hist1.p};
-    uint32_t* rows[2] = {a.rows, a.rows_alt};
-    int32_t* gh[2] = {a.gh, a.gh_alt};
-    const bool use_gh = a.gh != nullptr && a.gh_alt != nullptr && a.mode == 2;
-    P.T = T;
-    P.S = S;
-    P.chunk_rows = (int)a.chunk_rows;
-    P.n_groups = n_groups;
-    P.n_sc = n_sc;
-    P.newton = (a.mode == 2 && a.kind == 3 && S >= 2 && !(std::getenv("TMOG_TREE_HESS_GATE") &&
-                                                            std::getenv("TMOG_TREE_HESS_GATE")[0] == '0')) ? 1 : 0;
-    P.subtract = 1;
-    P.pair_fuse = 1;
-    P.F_use = F_use;
-    P.hsz = hsz;
-    P.live_dense = L.live_dense;
-    P.groups = (const tmog::FeatGroup*)(K + o_groups);
-    P.j_depth = (const int32_t*)(K + o_depth);
-    P.j_model = (const int32_t*)(K + o_model);
-    P.j_count = (const int64_t*)(K + o_count);
-    P.j_inst = (const double*)(K + o_inst);
-    P.j_gain = (const double*)(K + o_gain);
-    P.j_mcw = (const double*)(K + o_mcw);
-    P.j_lam = (const double*)(K + o_lam);
-    P.j_eps = (const double*)(K + o_eps);
-    P.r_feat = r_feat;
-    P.r_bin = r_bin;
-    P.r_gain = r_gain;
-    P.r_left = r_left;
-    P.r_tot = r_tot;
-    P.r_dl = r_dl;
-    P.r_cur = r_cur;
-    P.rec = io->rec;
-    P.W = W;
-    P.level_off = level_off;
-    P.cnt = cnt;
-    P.leaf_pos = leaf_pos;
-    P.cap_nl = cp.cap_nl;
-    P.cap_m = cp.cap_m;
-    P.cap_nodes = cp.cap_nodes;
-    P.cap_h = cp.cap_h;
-    P.cap_c = cp.cap_c;
-    P.cap_l = cp.cap_l;
-    P.has_missing = a.missing_bin >= 0 ? 1 : 0;
-    const int32_t* flist_d = (const int32_t*)(K + o_flist);
-    // levels 0..D build histograms (level D only when D == 0: deeper, no node of level D may split), and
-    // planner scratch in LDS when the per-level node capacity fits (TMOG_PLAN_LDS=0: global memory)
-    static const bool plan_lds_ok = [] { const char* e = std::getenv("TMOG_PLAN_LDS"); return !(e && e[0] == '0'); }();
-    const size_t per_node = (size_t)kPlanScratch * sizeof(int64_t) + sizeof(int32_t);
-    static const bool lds_attr = hipFuncSetAttribute((const void*)level_plan_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 148 * 1024) ==
-                                 hipSuccess;   // once per process (thread-safe static initialisation)
-    const bool lds_fit = plan_lds_ok && lds_attr && cp.cap_nl > 0 &&
-                         per_node * (size_t)cp.cap_nl + 64 <= (size_t)148 * 1024;
-    P.lds_cap = lds_fit ? cp.cap_nl : 0;
-    // threads of the two single-workgroup kernels (plan, finalisation); TMOG_PLAN_THREADS = 256 / 512 / 1024: a
-    // smaller workgroup finds a CU sooner while the other boosting parts' histogram waves occupy the chip
-    static const int plan_nt = [] {
-      const char* e = std::getenv("TMOG_PLAN_THREADS");
-      const int v = e ? std::atoi(e) : 1024;
-      return (v == 256 || v == 512) ? v : 1024;
-    }();
-    const size_t plan_lds = lds_fit ? per_node * (size_t)cp.cap_nl + 64 : 0;
-    // plan D + 1 turns the last decisions into leaves
-    for (int d = 0; d <= cp.D + 1; ++d) {
-      P.d = d;
-      hipLaunchKernelGGL(level_plan_kernel, dim3(1), dim3(plan_nt), plan_lds, st, P);
-      kchk((int)hipGetLastError(), "level_plan");
-      const int64_t nprev = d > 0 ? cp.nmax[d - 1] : 0;
-      const int64_t lbound = tmog::leaf_items_bound(a.chunk_rows, total, nprev) +
-                             tmog::leaf_items_bound(a.chunk_rows, total, cp.nmax[d]);
-      kchk(tmog_hip_leaf_collect(rows[0], P.litems, (int)std::min(lbound, cp.cap_l), a.leaf_rows, a.leaf_gid, st,
-                                 rows[1], cnt + C_NL),
-           "leaf_collect");
-      if (d > cp.D || (d == cp.D && d > 0)) continue;
-      const int c = d & 1;
-      const int64_t mb = cp.nmax[d];
-      kchk(tmog_hip_zero_segments(hist[c], P.zoff, P.zsize, (int)mb, hsz, L.live_dense, B * S, S, st, 0, cnt + C_NZ),
-           "zero_segments");
-      const int64_t hb = tmog::hist_items_bound(groups.data(), n_groups, a.chunk_rows, n_sc, total, mb);
-      kchk(tmog_hip_hist_build(a.Xb, a.F, rows[c], P.hitems, (int)std::min(hb, cp.cap_h),
-                               P.nfo, flist_d, P.nmd[c], P.nho[c], hist[c], B, a.mode, S, a.y, a.t1, a.t2, a.stride,
-                               a.qscale, a.mode == 2 ? a.missing_bin : -1, a.csr_ptr, a.csr_col, S, 0,
-                               need_general ? 1 : 0, st, use_gh ? gh[c] : nullptr, cnt + C_NH, a.wide_rows, a.Xh,
-                               a.Fh),
-           "hist_build");
-      if (d > 0)
-        kchk(tmog_hip_pair_scan(hist[c], hist[c ^ 1], P.poff, P.sj, P.bj, (int)std::max<int64_t>(1, mb / 2), P.nho[c],
-                                P.nnf, P.nfo, flist_d, a.n_bins, B, S, a.kind, P.par[c], a.missing_bin, P.nmd[c],
-                                a.qinv, F_use, sl.cand.p, L.split_n_multi, st, cnt + C_NP),
-             "pair_scan");
-      kchk(tmog_hip_split_find(hist[c], (int)mb, P.nho[c], P.nnf, P.nfo, flist_d, a.n_bins, B, S, a.kind, P.par[c],
-                               a.missing_bin, P.nmd[c], a.qinv, F_use, sl.cand.p, r_feat, r_bin, r_gain, r_dl, r_left,
-                               r_tot, r_cur, L.split_n_multi, fp ? sl.fp_send.p : nullptr, fp ? (int64_t)fp_rb : 0,
-                               fp ? a.fp_mlo : 0, fp ? L.fp_nml : 0, fp ? L.fp_obase : 0, st, (unsigned*)sl.done.p,
-                               cnt + C_M),
-           "split_find");
-      if (fp) {
-        // the ranks' best split per node: all-gather the level's records (the host bound mb of them; the
-        // merge reads the device count) and merge them into this level's decisions, all on the stream
-        kchk(tmog_hip_fp_allgather(sl.fp_send.p, sl.fp_recv.p, (int64_t)(fp_rb * (size_t)mb), a.fp_comm[0],
-                                   a.fp_world, st),
-             "fp_allgather");
-        kchk(tmog_hip_fp_merge_dev(sl.fp_recv.p, a.fp_world, (int)mb, (int64_t)fp_rb, S, r_feat, r_bin, r_gain,
-                                   r_dl, r_left, cnt + C_M, st),
-             "fp_merge");
-      }
-      kchk(tmog_hip_partition_fused(a.Xb, a.F, rows[c], rows[c ^ 1], P.citems,
-                                    (int)std::min(tmog::part_items_bound(total, mb), cp.cap_c), P.nb[c],
-                                    P.nc[c], r_feat, r_bin, r_dl, P.par[c], r_gain, a.missing_bin, r_cur, a.XbT, a.N,
-                                    st, use_gh ? gh[c] : nullptr, use_gh ? gh[c ^ 1] : nullptr, cnt + C_NC,
-                                    a.wide_rows),
-           "partition_fused");
-    }
-    Fa.T = T;
-    Fa.S = S;
-    Fa.mode = a.mode;
-    Fa.kind = a.kind;
-    Fa.n_levels = cp.D + 1;
-    Fa.rec = io->rec;
-    Fa.W = W;
-    Fa.level_off = level_off;
-    Fa.cnt = cnt;
-    Fa.leaf_pos = leaf_pos;
-    Fa.j_lam = P.j_lam;
-    Fa.j_eta = (const double*)(K + o_eta);
-    Fa.j_gamma = (const double*)(K + o_gam);
-    Fa.gid_value = io->gid_value;
-    Fa.gid_tree = io->gid_tree;
-    Fa.prune = 0;
-    for (int j = 0; j < T; ++j) Fa.prune |= io->job_gamma[j] > 0.0 ? 1 : 0;
-    hipLaunchKernelGGL(tree_finalize_kernel, dim3(1), dim3(plan_nt), 0, st, Fa);
-    kchk((int)hipGetLastError(), "tree_finalize");
+    Ctx c{a, *io, sl, (hipStream_t)a.stream, tmog::group_layout<true>(a, false, a.fp_world > 0)};
+    c.cp = caps_of(a, c.L, kNsc);
+    if (io->cap_nodes < c.cp.cap_nodes) throw std::runtime_error("record buffer too small");
+    c.hsz = (int64_t)c.L.F_use * a.B * a.S;
+    c.need_general = tmog::node_work(tmog::kNodeNeed, 1, a.chunk_rows, c.L.full_groups.data(),
+                                     (int)c.L.full_groups.size(), kNsc, c.L.live_dense, c.hsz).n_general > 0;
+    c.K = ship_constants(c);
+    Carve probe{nullptr};
+    lay_out(probe, c.cp, a.S);
+    sl.arena.need(probe.off + 256, slack(probe.off + 256), c.st);
+    Carve cv{sl.arena.as()};
+    c.A = lay_out(cv, c.cp, a.S);
+    reserve(c);
+    c.plan = plan_args(c);
+    for (int d = 0; d <= c.cp.D + 1; ++d) enqueue_level(c, d);
+    enqueue_finalize(c);
     return 0;
   } catch (const std::exception& e) {
     g_err = e.what();
