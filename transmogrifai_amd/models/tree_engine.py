@@ -1168,6 +1168,125 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
     return [out[int(mro[m]):int(mro[m + 1])] for m in range(len(model_rows))]
 
 
+# --------------------------------------------------------------------------------- staged evaluation
+EVAL_STAGES = 16            # stages per launch: bounds the aupr tables (16 x 2 x 65536 x 4 B = 8 MiB)
+EVAL_BINS = 1 << 16         # score bins of the aupr tables (the boosting epilogue's AUC_BINS)
+EVAL_BLOCK = N.ABI_CONSTS["TMOG_EVAL_BLOCK"]
+# metric name -> (native code, how the per-stage sum / count / table becomes the value the user reads)
+_EVAL_METRICS = {"logloss": ("TMOG_EVAL_LOGLOSS", "mean"), "error": ("TMOG_EVAL_ERROR", "mean"),
+                 "aucpr": ("TMOG_EVAL_AUPR", "aupr"), "rmse": ("TMOG_EVAL_SQERR", "rmse"),
+                 "mse": ("TMOG_EVAL_SQERR", "mean"), "mae": ("TMOG_EVAL_ABSERR", "mean"),
+                 "mlogloss": ("TMOG_EVAL_MLOGLOSS", "mean"), "merror": ("TMOG_EVAL_MERROR", "mean")}
+EVAL_MAXIMISED = ("aucpr",)
+
+
+def forest_staged_eval_raw(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor], y: torch.Tensor, *,
+                           stage_off, tree_col=None, K: int = 1, tree_weight=None, metric: str,
+                           margin_scale: float = 1.0, margins: Optional[torch.Tensor] = None, base=0.0):
+    """What the staged evaluation accumulates, before :func:`forest_staged_eval` finishes it: ``(raw, margins)`` with
+    ``raw`` the per-stage floating sums (float64 ``[S]``), error counts (int64 ``[S]``) or aupr count tables (int32
+    ``[S, 2, EVAL_BINS]``), on the device of ``Xb``."""
+    if metric not in _EVAL_METRICS:
+        raise ValueError(f"unknown staged evaluation metric {metric!r} (one of {sorted(_EVAL_METRICS)})")
+    code = N.ABI_CONSTS[_EVAL_METRICS[metric][0]]
+    multi = metric in ("mlogloss", "merror")
+    K = int(K)
+    if K < 1 or (K != 1 and not multi):
+        raise ValueError(f"metric {metric} takes one margin per row, got K = {K}")
+    dev = Xb.device
+    Xb = Xb.contiguous()
+    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
+    T = forest.n_trees
+    so = np.asarray(stage_off, np.int64).reshape(-1)
+    if so.size < 1 or so[0] < 0 or so[-1] > T or (np.diff(so) < 0).any():
+        raise ValueError("stage_off must be non-decreasing tree indices within the forest")
+    S = int(so.size) - 1
+    tc = np.zeros(T, np.int32) if tree_col is None else np.asarray(tree_col, np.int32).reshape(-1)
+    if tc.shape[0] != T or (T and (tc.min() < 0 or tc.max() >= K)):
+        raise ValueError("tree_col must give every tree a column in [0, K)")
+    tw = np.ones(T, np.float32) if tree_weight is None else np.asarray(tree_weight, np.float32).reshape(-1)
+    if tw.shape[0] != T:
+        raise ValueError("tree_weight must have one entry per tree")
+    if forest.value.shape[1] != 1:
+        raise ValueError("staged evaluation takes trees with one value per node")
+    toff = np.asarray(forest.tree_off, np.int64)
+    if T and (toff[0] < 0 or toff[-1] > len(forest.nodes) or (np.diff(toff) < 1).any()):
+        raise ValueError("forest tree offsets out of range")
+    row_list = None
+    n = Nrows
+    if rows is not None:
+        row_list = rows.to(dev).to(torch.int32).contiguous()
+        n = int(row_list.numel())
+        if n and (int(row_list.min()) < 0 or int(row_list.max()) >= Nrows):
+            raise ValueError("row ids out of range")
+    yf = y.to(dev).to(torch.float32).contiguous()
+    if yf.numel() < Nrows:
+        raise ValueError("y must hold a label for every row of Xb")
+    if margins is None:
+        margins = torch.zeros(n, K, dtype=torch.float64, device=dev) + torch.as_tensor(
+            np.asarray(base, np.float64), device=dev)
+    else:
+        margins = margins.to(torch.float64).reshape(n, K).contiguous()
+    bins = EVAL_BINS
+    if metric == "aucpr":
+        raw = torch.zeros(S, 2, bins, dtype=torch.int32, device=dev)
+    elif metric in ("error", "merror"):
+        raw = torch.zeros(S, dtype=torch.int64, device=dev)
+    else:
+        raw = torch.zeros(S, dtype=torch.float64, device=dev)
+    if n == 0 or S == 0:
+        return raw, margins
+    pk = _Pack(dev)
+    for a in (toff[:-1], tw, np.ascontiguousarray(forest.nodes), forest.default_left,
+              np.ascontiguousarray(forest.value[:, 0], np.float32), so, tc):
+        pk.add(a)
+    t_off, t_w, nodes, dl, lv, so_t, tc_t = pk.ship()
+    on_gpu = dev.type == "cuda"
+    nblk = (n + EVAL_BLOCK - 1) // EVAL_BLOCK
+    slab = torch.empty(nblk * min(S, EVAL_STAGES), dtype=torch.float64, device=dev) \
+        if on_gpu and raw.dtype == torch.float64 else None
+    for s0 in range(0, S, EVAL_STAGES):
+        sc = min(EVAL_STAGES, S - s0)
+        part = raw[s0:s0 + sc]
+        args = (N.ptr(Xb), F, N.ptr(row_list), n, N.ptr(yf), N.ptr(nodes), N.ptr(dl), N.ptr(lv), N.ptr(t_off),
+                N.ptr(t_w), int(forest.missing_bin), N.ptr(so_t[s0:]), sc, N.ptr(tc_t), K, code, float(margin_scale),
+                bins, N.ptr(margins), N.ptr(part) if raw.dtype == torch.float64 else None,
+                N.ptr(part) if raw.dtype == torch.int64 else None, N.ptr(part) if raw.dtype == torch.int32 else None)
+        if on_gpu:
+            N.check(N.hip().tmog_hip_forest_staged_eval(*args, N.ptr(slab), N.stream(dev)), "forest_staged_eval")
+        else:
+            N.check(N.host().tmog_forest_staged_eval_cpu(*args), "forest_staged_eval_cpu")
+    return raw, margins
+
+
+def staged_eval_finish(raw: torch.Tensor, n: int, metric: str) -> np.ndarray:
+    """The metric values (float64 ``[S]``, as the user reads them) of :func:`forest_staged_eval_raw`'s ``raw``."""
+    how = _EVAL_METRICS[metric][1]
+    if how == "aupr":
+        from ..evaluators.metrics import binned_aupr_from_counts
+        return binned_aupr_from_counts(raw).cpu().numpy().astype(np.float64)
+    v = raw.cpu().numpy().astype(np.float64) / max(n, 1)
+    return np.sqrt(v) if how == "rmse" else v
+
+
+def forest_staged_eval(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor], y: torch.Tensor, *,
+                       stage_off, tree_col=None, K: int = 1, tree_weight=None, metric: str,
+                       margin_scale: float = 1.0, margins: Optional[torch.Tensor] = None, base=0.0):
+    """The metric of a boosted model after each of its stages, in one pass over the trees.
+
+    Stage ``s`` is the trees ``stage_off[s]..stage_off[s + 1]`` of ``forest``; tree ``t`` adds ``tree_weight[t]`` times
+    its leaf value to column ``tree_col[t]`` of the rows' fp64 margins (``[n, K]``, started at ``base`` or at
+    ``margins``, the margins an earlier call returned). ``rows`` are row ids into ``Xb`` (None: every row), ``y`` the
+    labels by row id. ``metric``: ``logloss`` / ``error`` / ``aucpr`` of the probability ``1 / (1 + exp(-margin_scale
+    * margin))``, ``rmse`` / ``mse`` / ``mae``, or ``mlogloss`` / ``merror`` over K margins. Returns ``(values, margins)``:
+    the metric after each stage (numpy float64 ``[S]``) and the margins after the last one. At most ``EVAL_STAGES``
+    stages go into one launch. CUDA tensors run ``staged_eval_kernel``, others the host twin."""
+    raw, margins = forest_staged_eval_raw(forest, Xb, rows, y, stage_off=stage_off, tree_col=tree_col, K=K,
+                                          tree_weight=tree_weight, metric=metric, margin_scale=margin_scale,
+                                          margins=margins, base=base)
+    return staged_eval_finish(raw, int(margins.shape[0]), metric), margins
+
+
 # ------------------------------------------------------------------------------------------ TreeSHAP
 @dataclass
 class ForestPaths:

@@ -10,7 +10,9 @@ normalized leaf distributions, GBT log-loss boosting on {-1, +1} labels with ``1
 XGBoost: second-order gain, ``min_child_weight``, ``lambda``, ``gamma`` post-pruning, ``eta``-scaled
 leaves, learned default direction for missing values (``missing`` = 0.0 by default in the
 reference grid), early stopping on the training ``aucpr``; the multiclass softmax objectives grow one tree
-per class and round (early stopping on the training ``merror`` / ``mlogloss``).
+per class and round (early stopping on the training ``merror`` / ``mlogloss``). With ``train_test_ratio < 1``
+(XGBoost4J-Spark's ``trainTestRatio``) the rows :func:`watch_split` holds out are the watch early stopping reads
+instead, on ``eval_metric``; ``staged_eval`` gives a boosted model's metric after every round.
 
 Every (config x fold x tree) of a learner grows in the same level-synchronous forest; boosting
 learners advance all their models one round per engine call.
@@ -165,6 +167,18 @@ def bootstrap_weights_multi(rows: torch.Tensor, seeds, rate: float) -> torch.Ten
 
 def _rows(job: FitJob, N, dev):
     return torch.arange(N, device=dev) if job.rows is None else job.rows.to(dev)
+
+
+WATCH_STREAM = 29           # row_uniform stream of the held-out watch split
+
+
+def watch_split(rows: torch.Tensor, ratio: float, seed: int, with_mask: bool = False):
+    """``(training rows, watch rows)`` of a boosting job with ``train_test_ratio = ratio``: a row trains when its
+    counter-based uniform (of the global row id and the seed only) is below ``ratio``, else it is in the evaluation
+    watch that early stopping reads. Row order is kept. ``with_mask``: also the boolean training mask over ``rows``."""
+    keep = row_uniform(rows, int(seed), WATCH_STREAM) < float(ratio)
+    out = (rows[keep], rows[~keep])
+    return out + (keep,) if with_mask else out
 
 
 def _add_tree_margins(Fm: torch.Tensor, forest: "TE.Forest", Xb, act: List[int], wgts: List[float],
@@ -550,6 +564,21 @@ class _BoostLearner(Learner):
             gjobs = [jobs[i] for i in idxs]
             yd = y.to(dev)
             NU = N
+            # held-out watch (train_test_ratio < 1): split by global row id here, before union_rows remaps the ids;
+            # the watch rows keep their ids into the full Xb / y, only the training rows reach the grower
+            watched = [None] * len(gjobs)
+            if self.watch_metrics is not None:
+                for k, j in enumerate(gjobs):
+                    ratio = float(j.params.get("train_test_ratio", 1.0))
+                    if ratio < 1.0:
+                        self._watch_metric(j.params)
+                        tr, wr, keep = watch_split(_rows(j, N, dev), ratio, int(j.params.get("seed", 0)),
+                                                   with_mask=True)
+                        if wr.numel() == 0:
+                            raise ValueError(f"train_test_ratio={ratio} leaves no watch rows")
+                        gjobs[k] = FitJob(j.params, tr, None if j.weights is None else j.weights.to(dev)[keep])
+                        watched[k] = wr
+            watch_data = (Xb, yd) if any(w is not None for w in watched) else None
             if all(j.rows is not None for j in gjobs):
                 # boost only over the union of the jobs' training rows: gradients, margins and the
                 # per-round prediction pass then scale with the (down-sampled) training sets, not N
@@ -561,10 +590,21 @@ class _BoostLearner(Learner):
                     gjobs = [FitJob(j.params, r, j.weights) for j, r in zip(gjobs, parts)]
             res = []
             for lo, hi in _budget_chunks([_boost_job_bytes(j, NU, F, key[0], self.pseudo_jobs) for j in gjobs], dev):
-                res += self._boost(Xb, spec, yd, gjobs[lo:hi], NU, F, dev, key[0], par=_par(context))
+                kw = {} if watch_data is None else {"watch": watch_data + (watched[lo:hi],)}
+                res += self._boost(Xb, spec, yd, gjobs[lo:hi], NU, F, dev, key[0], par=_par(context), **kw)
             for k, i in enumerate(idxs):
                 out[i] = res[k]
         return out
+
+    # eval_metric -> tree_engine metric of the held-out watch; None: the learner takes no train_test_ratio
+    watch_metrics: Optional[Dict[str, str]] = None
+
+    def _watch_metric(self, params) -> str:
+        em = str(params.get("eval_metric", self.defaults.get("eval_metric")))
+        if em not in self.watch_metrics:
+            raise ValueError(f"eval_metric {em} not supported for {self.name}'s held-out watch "
+                             f"(one of {sorted(self.watch_metrics)})")
+        return em
 
     def _bin_key(self, p):
         return (int(p.get("max_bins", 32)), None, False)
@@ -598,8 +638,31 @@ class _BoostLearner(Learner):
     def predict(self, state, X, context=None):
         return self._outputs(state, self.margin(state, X, None, context))
 
+    margin_scale = 1.0          # probability = 1 / (1 + exp(-margin_scale * margin))
+
+    def staged_eval(self, state, X, y, metric=None, rows=None, context=None) -> np.ndarray:
+        """The validation curve of a fitted model: ``metric`` on ``rows`` of ``(X, y)`` (None: every row) after
+        each boosting round, float64 ``[rounds]``, from one pass over the trees (``TE.forest_staged_eval``).
+        ``metric``: ``logloss`` / ``error`` / ``aucpr`` for a binary model, ``rmse`` / ``mse`` / ``mae`` for a regressor
+        (or the squared-error classifier), ``mlogloss`` / ``merror`` for a multiclass model, whose round is its K
+        trees; by default the model's own loss (``logloss``, ``rmse``, ``mlogloss``)."""
+        forest, Xb = self._binned_for(state, X, context)
+        multi = state.get("objective") in MULTI_OBJECTIVES
+        K = int(state["n_classes"]) if multi else 1
+        if metric is None:
+            squared = not self.classification or state.get("objective") == "reg:squarederror"
+            metric = "mlogloss" if multi else ("rmse" if squared else "logloss")
+        T = forest.n_trees
+        if T % K:
+            raise ValueError(f"{T} trees do not make whole rounds of {K} classes")
+        vals, _ = TE.forest_staged_eval(
+            forest, Xb, rows, y, stage_off=np.arange(0, T + 1, K), tree_col=np.arange(T) % K, K=K,
+            tree_weight=np.asarray(state["tree_weights"], np.float32), metric=metric,
+            margin_scale=self.margin_scale, base=float(state.get("base_margin", 0.0)))
+        return vals
+
     def shap_values(self, state, X, rows=None, context=None):
-        """Exact TreeSHAP of the margin: ``(phi float64 [n, U + 1, C], used_features int64 [U])``, slot ``U``
+        """Exact TreeSHAP of the margin:``(phi float64 [n, U + 1, C], used_features int64 [U])``, slot ``U``
         the bias (``base_margin`` included). A regressor has one column, a binary classifier the two columns
         ``(-phi, +phi)`` of its raw prediction ``(-m, m)``, a multiclass model one per class (tree ``t``
         belongs to class ``t % K``)."""
@@ -630,6 +693,7 @@ class GBTClassifierLearner(_BoostLearner):
     defaults = {"max_depth": 5, "max_bins": 32, "min_instances_per_node": 1, "min_info_gain": 0.0, "max_iter": 20,
                 "step_size": 0.1, "subsampling_rate": 1.0, "impurity": "variance", "loss_type": "logistic",
                 "seed": 0}
+    margin_scale = 2.0          # Spark GBT: probability = 1 / (1 + exp(-2 F))
 
     def _target(self, yy, Fm, first):
         ys = 2 * yy - 1
@@ -1080,7 +1144,7 @@ def _remap_features(forest, colperm):
         forest.nodes[internal, 0] = colperm[forest.nodes[internal, 0]]
 
 
-def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb, par=None):
+def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb, par=None, watch=None):
     """The boosting rounds of every XGBoost learner: the states of ``jobs``, all advanced one round per grower call.
 
     ``make_objective(jobs, y, N, dev, fused=, amax=, resident=, wide=)`` builds what differs between objectives:
@@ -1090,11 +1154,23 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
     (``resident``), with the fused prologue (``prologue``, then ``stage()`` returns grow_forest's ``prestaged``) and
     with a lagged early-stopping read-back (``lagged``). Per part it gives ``begin(ps)`` (its scratch); per round
     ``grad_torch(act)`` before growth on the torch path, ``epilogue(...)`` after growth on the fused path (margins,
-    next statistics, maxima) and ``metric(need, aux)``: the early-stopping values, larger is better."""
+    next statistics, maxima) and ``metric(need, aux)``: the early-stopping values, larger is better.
+
+    ``watch = (Xb_w, y_w, rows, metrics)``: per job the held-out rows (ids into ``Xb_w`` / ``y_w``, the matrix binned as
+    ``spec`` in its original column order; None: no watch) and its ``(eval_metric, tree_engine metric)``. A watched
+    job's early stopping reads that metric on those rows (``TE.forest_staged_eval``, once per chunk of rounds)
+    instead of the training metric, with the same rule; the rounds grown past the stopping point are trimmed, so
+    the model does not depend on the chunk size."""
     t_setup0 = time.perf_counter()
     P = len(jobs)
     rounds = [int(j.params.get("num_round", 100)) for j in jobs]
-    esr = [int(j.params.get("num_early_stopping_rounds", 0)) if early_stopping else 0 for j in jobs]
+    wrows = list(watch[2]) if watch is not None else [None] * P
+    wmetric = list(watch[3]) if watch is not None else [None] * P
+    esr = [int(j.params.get("num_early_stopping_rounds", 0)) if (early_stopping or wrows[p] is not None) else 0
+           for p, j in enumerate(jobs)]
+    wmargin: List[Optional[torch.Tensor]] = [None] * P     # watch margins after the rounds evaluated so far
+    whist: List[list] = [[] for _ in range(P)]             # watch metric per evaluated round
+    wdone = [0] * P
     forests, weights = [[] for _ in range(P)], [[] for _ in range(P)]
     best = [-float("inf")] * P
     best_round = [0] * P
@@ -1104,12 +1180,36 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
     fused = dev.type == "cuda" and all(float(j.params.get("subsample", 1.0)) >= 1.0 for j in jobs) and \
         os.environ.get("TMOG_XGB_FUSED", "1") != "0"
     Xg, n_bins_g, colperm, Xh, fp, csr, XgT = _xgb_growth_matrix(Xb, spec, dev, par)
+    if watch is not None and par is not None and fp is not None:
+        raise NotImplementedError("train_test_ratio < 1 (a held-out watch) is not supported in feature-parallel fits")
     wide = TE.wide_rows(int(Xg.shape[0]))
     # a feature-parallel job (fp: the jobs spread over a rank group) grows on the device-planned loop too, as one
     # job group whose level exchange (RCCL all-gather + merge of the split records) is enqueued on the stream
     obj = make_objective(jobs, y, N, dev, fused=fused, amax=fused and os.environ.get("TMOG_XGB_AMAX", "1") != "0",
                          resident=fused and (par is None or fp is not None) and TE.resident_enabled(), wide=wide)
     K, rows, Fm, amax_cur = obj.K, obj.rows, obj.Fm, obj.amax_cur
+    # A watched job's statistics stay zero outside its training rows (the softmax objective's always do): its
+    # quantisation maxima, and with them its trees, then do not depend on whether other jobs of the batch bring the
+    # job's own watch rows into the union.
+    own: Dict[int, torch.Tensor] = {}
+    if K == 1:
+        for p in range(P):
+            if wrows[p] is not None:
+                own[p] = torch.zeros(N, dtype=torch.bool, device=dev)
+                own[p][rows[p]] = True
+
+    def own_rows_only(ps):
+        for p in ps:
+            if p in own:
+                obj.G[p] = torch.where(own[p], obj.G[p], torch.zeros_like(obj.G[p]))
+                obj.H[p] = torch.where(own[p], obj.H[p], torch.zeros_like(obj.H[p]))
+
+    if obj.G is not None:
+        own_rows_only(range(P))
+        if amax_cur is not None:
+            for p in own:
+                amax_cur[p, 0], amax_cur[p, 1] = obj.G[p].abs().amax(), obj.H[p].abs().amax()
+                obj.comp[p] = 0
     resident, prologue = obj.resident, obj.prologue
     es_lag = max(1, int(os.environ.get("TMOG_ES_LAG", "2"))) if obj.lagged else 1
 
@@ -1122,7 +1222,46 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
         tick = time.perf_counter
         pending: list = []
         deferred: list = []        # (pseudo-jobs, ResidentTree) per device-planned round, in round order
+        cursor = {p: 0 for p in ps}
         part = obj.begin(ps)
+        wps = [p for p in ps if wrows[p] is not None]
+        # rounds between two readings of the watch: the stopping rule cannot fire sooner than the patience
+        wchunk = max(1, int(os.environ.get("TMOG_XGB_WATCH_CHUNK") or
+                            min([esr[p] for p in wps if esr[p] > 0] + [TE.EVAL_STAGES])))
+
+        def flush_deferred():
+            """Host Forests of the device-planned rounds since the last flush: one device->host copy."""
+            fs = TE.resident_forests([rt for _, rt in deferred])
+            for (qact_r, _), f in zip(deferred, fs):
+                _remap_features(f, colperm)
+                for k_, q in enumerate(qact_r):
+                    p = q // K
+                    while forests[p][cursor[p]] is not None:
+                        cursor[p] += 1
+                    forests[p][cursor[p]] = f.tree(k_)
+            deferred.clear()
+
+        def watch_eval():
+            """The watch metric of every round grown since the last reading, and the stopping rule on it."""
+            flush_deferred()
+            for p in wps:
+                a, grown = wdone[p], len(forests[p]) // K
+                if stopped[p] or grown <= a:
+                    continue
+                nt = (grown - a) * K
+                vals, wmargin[p] = TE.forest_staged_eval(
+                    TE.Forest.concat(forests[p][a * K:grown * K]), watch[0], wrows[p], watch[1],
+                    stage_off=np.arange(0, nt + 1, K), tree_col=np.arange(nt) % K, K=K, metric=wmetric[p][1],
+                    margins=wmargin[p], base=obj.base[p])
+                wdone[p] = grown
+                sign = 1.0 if wmetric[p][1] in TE.EVAL_MAXIMISED else -1.0
+                for r, v in enumerate(vals.tolist(), start=a):
+                    whist[p].append(v)
+                    if sign * v > best[p] + 1e-12:
+                        best[p], best_round[p] = sign * v, r
+                    elif esr[p] > 0 and r - best_round[p] >= esr[p]:
+                        stopped[p] = True
+                        break
 
         def resolve(it0, need0, vals_t):
             for p, v in zip(need0, vals_t.tolist()):
@@ -1141,6 +1280,7 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
             t_0 = tick()
             if not fused:
                 obj.grad_torch(act)
+                own_rows_only(act)
             tjobs = []
             for p in act:
                 pr = jobs[p].params
@@ -1177,7 +1317,7 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
             is_res = isinstance(forest, TE.ResidentTree)
             if not is_res:
                 _remap_features(forest, colperm)
-            need = [p for p in act if esr[p] > 0]
+            need = [p for p in act if esr[p] > 0 and wrows[p] is None]
             aux = None
             if fused:
                 aux = obj.epilogue(it, act, qact, forest, need, part)
@@ -1200,6 +1340,8 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
                 while len(pending) >= es_lag:
                     resolve(*pending.pop(0))
                 pending.append((it, need, vals_t))
+            if wps and (it + 1) % wchunk == 0:
+                watch_eval()
             if prof is not None:
                 t_4 = tick()
                 for k_, v_ in (("pre", t_1 - t_0), ("grow", t_2 - t_1), ("post", t_3 - t_2), ("es", t_4 - t_3)):
@@ -1207,16 +1349,10 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
                 prof["rounds"] = prof.get("rounds", 0) + 1
         while pending:
             resolve(*pending.pop(0))
+        if wps:
+            watch_eval()
         if deferred:
-            fs = TE.resident_forests([rt for _, rt in deferred])
-            cursor = {p: 0 for p in ps}
-            for (qact_r, _), f in zip(deferred, fs):
-                _remap_features(f, colperm)
-                for k_, q in enumerate(qact_r):
-                    p = q // K
-                    while forests[p][cursor[p]] is not None:
-                        cursor[p] += 1
-                    forests[p][cursor[p]] = f.tree(k_)
+            flush_deferred()
 
     # Pipelined job parts (GPU, fused path): the models are split into parts (cut between models, never inside
     # one), each boosted by its own host thread on its own stream, so one part's per-round host work (tree
@@ -1244,6 +1380,10 @@ def _newton_boost(make_objective, early_stopping, Xb, spec, y, jobs, N, dev, mb,
         res.append({"forest": TE.Forest.concat(forests[p][:keep]).to_state(), "bins": spec.to_state(),
                     "tree_weights": np.asarray(weights[p][:keep], np.float32), "n_classes": obj.n_classes,
                     "max_bins": mb, "base_margin": obj.base[p], "num_trees": keep})
+        if wrows[p] is not None:
+            res[-1].update(eval_metric=wmetric[p][0], eval_history=np.asarray(whist[p], np.float64),
+                           best_iteration=int(best_round[p]),
+                           train_test_ratio=float(jobs[p].params.get("train_test_ratio", 1.0)))
     return res
 
 
@@ -1282,17 +1422,28 @@ class XGBoostClassifierLearner(_BoostLearner):
     defaults = {"num_round": 100, "eta": 0.3, "gamma": 0.0, "max_depth": 6, "min_child_weight": 1.0,
                 "reg_lambda": 1.0, "missing": float("nan"), "max_bins": 64, "num_early_stopping_rounds": 0,
                 "eval_metric": "aucpr", "maximize_evaluation_metrics": True, "objective": "binary:logistic",
-                "base_score": 0.5, "subsample": 1.0, "colsample_bytree": 1.0, "seed": 0, "num_class": None}
+                "base_score": 0.5, "subsample": 1.0, "colsample_bytree": 1.0, "seed": 0, "num_class": None,
+                "train_test_ratio": 1.0}
     _objective = _LogisticObjective
+    watch_metrics = {"aucpr": "aucpr", "logloss": "logloss", "error": "error"}
 
     def _bin_key(self, p):
         miss = p.get("missing", float("nan"))
         mv = None if (miss is None or (isinstance(miss, float) and math.isnan(miss))) else float(miss)
         return (int(p.get("max_bins", 64)), mv, True)
 
-    def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None):
-        # early stopping (on the training metric) is the classifiers': the regressor grows all its rounds
-        return _newton_boost(self._objective, self.classification, Xb, spec, y, jobs, N, dev, mb, par)
+    def _watch(self, watch, jobs):
+        """``_newton_boost``'s watch: the rows fit_batch held out, with each watched job's metric."""
+        if watch is None:
+            return None
+        return watch + ([None if r is None else (self.watch_metrics[self._watch_metric(j.params)],) * 2
+                         for r, j in zip(watch[2], jobs)],)
+
+    def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None, watch=None):
+        # early stopping on the training metric is the classifiers': the regressor grows all its rounds unless it
+        # has a held-out watch (train_test_ratio < 1)
+        return _newton_boost(self._objective, self.classification, Xb, spec, y, jobs, N, dev, mb, par,
+                             self._watch(watch, jobs))
 
     def fit_batch(self, X, y, jobs, context=None):
         """Jobs with ``objective="reg:squarederror"`` (xgboost4j's own default, which a bare
@@ -1355,6 +1506,7 @@ class XGBoostClassifierLearner(_BoostLearner):
 class _SquaredErrorXGBClassifier(XGBoostClassifierLearner):
     """Squared-error boosting of a 0/1 label (see :meth:`XGBoostClassifierLearner.fit_batch`); not registered."""
     _objective = _SquaredErrorObjective
+    watch_metrics = {"aucpr": "aucpr", "rmse": "rmse", "mae": "mae"}    # aucpr: of sigmoid(margin), as in training
 
 
 class _SoftmaxXGBClassifier(XGBoostClassifierLearner):
@@ -1372,8 +1524,11 @@ class _SoftmaxXGBClassifier(XGBoostClassifierLearner):
     def pseudo_jobs(self):
         return self.K
 
-    def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None):
-        res = _newton_boost(functools.partial(_SoftmaxObjective, self.K), True, Xb, spec, y, jobs, N, dev, mb, par)
+    watch_metrics = {"aucpr": "merror", "merror": "merror", "mlogloss": "mlogloss"}
+
+    def _boost(self, Xb, spec, y, jobs, N, F, dev, mb, par=None, watch=None):
+        res = _newton_boost(functools.partial(_SoftmaxObjective, self.K), True, Xb, spec, y, jobs, N, dev, mb, par,
+                            self._watch(watch, jobs))
         return [dict(r, objective=str(j.params.get("objective", "multi:softprob"))) for r, j in zip(res, jobs)]
 
 
@@ -1385,6 +1540,7 @@ class XGBoostRegressorLearner(XGBoostClassifierLearner):
     defaults = dict(XGBoostClassifierLearner.defaults, objective="reg:squarederror", eval_metric="rmse",
                     maximize_evaluation_metrics=False)
     _objective = _SquaredErrorObjective
+    watch_metrics = {"rmse": "rmse", "mae": "mae"}
 
     def _outputs(self, state, m):
         e = torch.zeros(m.shape[0], 0, dtype=torch.float64, device=m.device)

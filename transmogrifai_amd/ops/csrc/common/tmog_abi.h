@@ -22,6 +22,16 @@
 #define TMOG_PART_ITEM_ROWS 1024   // rows per partition item (GPU)
 #define TMOG_PM_VK 32              // forest_predict_multi_kernel: variants x classes accumulated per thread
 
+// ---- metrics of the staged forest evaluation (common/boost_eval.hpp has the per-row terms)
+#define TMOG_EVAL_LOGLOSS 0        // binary, K = 1: floating sum
+#define TMOG_EVAL_ERROR 1          // binary: count
+#define TMOG_EVAL_AUPR 2           // binary: [2][bins] count table per stage
+#define TMOG_EVAL_SQERR 3          // regression: floating sum
+#define TMOG_EVAL_ABSERR 4         // regression: floating sum
+#define TMOG_EVAL_MLOGLOSS 5       // K classes: floating sum
+#define TMOG_EVAL_MERROR 6         // K classes: count
+#define TMOG_EVAL_BLOCK 256        // rows per workgroup of the kernel: its slab holds ceil(n / 256) x S partial sums
+
 // ---- flags of a histogram item (HistItem.excl); REG, CSR and WIDE are also the flags of a feature group
 #define TMOG_ITEM_SOLE 1           // this item alone covers the node's rows for its features (plain stores)
 #define TMOG_ITEM_REG 2            // every feature of the group has one present bin (register accumulation)
@@ -215,6 +225,18 @@ int tmog_forest_predict_cpu(const uint8_t* Xb, int F, int n_models, const int64_
                             const int32_t* row_list, const int64_t* model_tree_off, const int64_t* tree_off,
                             const float* tree_weight, const int32_t* nodes, const uint8_t* default_left,
                             int missing_bin, const float* leaf_value, int K, float* out);
+// Staged evaluation of a boosted forest on rows row_list[0..n) (null: rows 0..n-1): for s in [0, S) the trees
+// stage_off[s]..stage_off[s + 1] are walked (tree t starts at node tree_off[t]; leaf_value is [n_nodes][1]), margins[i]
+// [tree_col[t]] += (double)tree_weight[t] * (double)leaf_value (margins is [n][K] fp64, in/out), then the metric of the
+// updated margins over the n rows is stored: values[s] (floating sums, added in row order), counts[s] += (error
+// counts) or tables[s][2][bins] += (aupr); the buffers a metric does not use may be null. y is indexed by row id.
+// Returns non-zero for an unknown metric or a binary / regression metric with K != 1.
+int tmog_forest_staged_eval_cpu(const uint8_t* Xb, int F, const int32_t* row_list, int64_t n, const float* y,
+                                const int32_t* nodes, const uint8_t* default_left, const float* leaf_value,
+                                const int64_t* tree_off, const float* tree_weight, int missing_bin,
+                                const int64_t* stage_off, int S, const int32_t* tree_col, int K, int metric,
+                                double scale, int bins, double* margins, double* values, int64_t* counts,
+                                int32_t* tables);
 int tmog_forest_shap_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
                          int64_t P, const int64_t* p_off, const int32_t* p_out, const double* p_val, int KV,
                          const double* bias, const int32_t* e_feat, const int32_t* e_rng, const double* e_z,

@@ -230,6 +230,15 @@ int tmog_hip_forest_predict(const uint8_t* Xb, int F, int n_models, const int64_
                             const uint8_t* default_left, int missing_bin, const float* leaf_value, int K, float* out,
                             hipStream_t stream);
 
+// ---- hip/staged_eval_kernels.hip: the contract of tmog_forest_staged_eval_cpu (common/tmog_abi.h); slab holds
+// ceil(n / TMOG_EVAL_BLOCK) x S doubles, the per-workgroup partial sums that values[] is reduced from in a fixed order
+int tmog_hip_forest_staged_eval(const uint8_t* Xb, int F, const int32_t* row_list, int64_t n, const float* y,
+                                const int32_t* nodes, const uint8_t* default_left, const float* leaf_value,
+                                const int64_t* tree_off, const float* tree_weight, int missing_bin,
+                                const int64_t* stage_off, int S, const int32_t* tree_col, int K, int metric,
+                                double scale, int bins, double* margins, double* values, int64_t* counts,
+                                int32_t* tables, double* slab, hipStream_t stream);
+
 // ---- hip/tree_resident.hip: device-planned growth of one job group on the caller's stream
 int64_t tmog_hip_resident_cap_nodes(const GrowArgs* args);
 int tmog_hip_plan_profile(uint64_t* out, int reset);

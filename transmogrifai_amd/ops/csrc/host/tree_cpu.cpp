@@ -28,8 +28,9 @@
 
 #include "common/tmog_abi.h"
 #include "common/tree_rules.hpp"
+#include "common/boost_eval.hpp"
 
-using namespace tmog;   // the split / growth rules shared with the HIP twins
+using namespace tmog;  // the split / growth rules shared with the HIP twins
 
 constexpr int kMaxS = 256;   // statistics per bin (classes); the HIP wide path has the same bound
 
@@ -232,6 +233,62 @@ int tmog_forest_predict_cpu(const uint8_t* Xb, int F, int n_models, const int64_
         const float w = tree_weight[t];
         for (int c = 0; c < K; ++c) o[c] += w * leaf_value[k * K + c];
       }
+    }
+  }
+  return 0;
+}
+
+// -------------------------------------------------------------------------------- staged evaluation
+// Host twin of ../hip/staged_eval_kernels.hip (contract in common/tmog_abi.h): the trees of a stage are walked and
+// added per row in tree order, then the stage's metric is taken over the rows in row order.
+int tmog_forest_staged_eval_cpu(const uint8_t* Xb, int F, const int32_t* row_list, int64_t n, const float* y,
+                                const int32_t* nodes, const uint8_t* default_left, const float* leaf_value,
+                                const int64_t* tree_off, const float* tree_weight, int missing_bin,
+                                const int64_t* stage_off, int S, const int32_t* tree_col, int K, int metric,
+                                double scale, int bins, double* margins, double* values, int64_t* counts,
+                                int32_t* tables) {
+  if (!eval_metric_known(metric) || K < 1 || (!eval_metric_multi(metric) && K != 1)) return 1;
+  if (n <= 0 || S <= 0) return 0;
+  std::vector<double> term(eval_metric_counted(metric) || metric == TMOG_EVAL_AUPR ? 0 : n);
+  std::vector<int32_t> mark(term.empty() ? n : 0);   // a row's error bit or table slot
+  for (int s = 0; s < S; ++s) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t row = row_list ? row_list[i] : i;
+      const uint8_t* xr = Xb + row * (int64_t)F;
+      double* mr = margins + i * K;
+      for (int64_t t = stage_off[s]; t < stage_off[s + 1]; ++t) {
+        int64_t k = tree_off[t];
+        while (nodes[4 * k + 2] >= 0) {
+          const auto dl = [&] { return default_left[k] != 0; };
+          const bool gl = goes_left(xr[nodes[4 * k]], nodes[4 * k + 1], dl, missing_bin);
+          k = gl ? nodes[4 * k + 2] : nodes[4 * k + 3];
+        }
+        mr[tree_col ? tree_col[t] : 0] += (double)tree_weight[t] * (double)leaf_value[k];
+      }
+      const float yr = y[row];
+      const auto mc = [&](int c) { return mr[c]; };
+      switch (metric) {
+        case TMOG_EVAL_LOGLOSS: term[i] = eval_logloss(mr[0], scale, (double)yr); break;
+        case TMOG_EVAL_ERROR: mark[i] = eval_error(mr[0], scale, (double)yr); break;
+        case TMOG_EVAL_AUPR: mark[i] = eval_aupr_slot(mr[0], scale, yr, bins); break;
+        case TMOG_EVAL_SQERR: term[i] = eval_sqerr(mr[0], (double)yr); break;
+        case TMOG_EVAL_ABSERR: term[i] = eval_abserr(mr[0], (double)yr); break;
+        case TMOG_EVAL_MLOGLOSS: term[i] = eval_mlogloss(mc, K, eval_label(yr, K)); break;
+        default: mark[i] = eval_merror(mc, K, (int)yr); break;
+      }
+    }
+    if (metric == TMOG_EVAL_AUPR) {
+      int32_t* tb = tables + (int64_t)s * 2 * bins;
+      for (int64_t i = 0; i < n; ++i) ++tb[mark[i]];
+    } else if (eval_metric_counted(metric)) {
+      int64_t c = 0;
+      for (int64_t i = 0; i < n; ++i) c += mark[i];
+      counts[s] += c;
+    } else {
+      double acc = 0.0;
+      for (int64_t i = 0; i < n; ++i) acc += term[i];
+      values[s] = acc;
     }
   }
   return 0;
