@@ -1,0 +1,152 @@
+"""Forest scoring: the node-image kernels against the kernels they replace (``TMOG_PREDICT_V1=1``).
+
+Synthetic binned rows (``--rows`` x F uint8) and synthetic forests, scored through ``tree_engine.forest_predict`` /
+``forest_predict_multi`` on listed rows (a shuffled held-out fold), the way cross-validation calls them:
+
+* ``multi``: ``--multi-trees`` trees of depth ``--multi-depth`` shared by nine pruned variants (max depth 3 / 6 / 12 x
+  min gain 0.001 / 0.01 / 0.1), K = 2: the random-forest grid's validation call (``forest_predict_multi_kernel``);
+* ``plain``: ``--plain-trees`` trees of depth ``--plain-depth``, K = 1: a boosted model's fold validation
+  (``forest_predict_lds_kernel`` at F <= 512, ``forest_predict_kernel`` above).
+
+Each case is timed with device events in one process, the two paths alternating, ``--runs`` times after one warm-up
+each. ``v1`` is the old path, ``image_cold`` the new one on a forest object that has no image yet (the image build
+and its upload are inside the timed region, as in a cross-validation that scores every forest once), ``image_warm``
+the new one on a forest that has been scored before (a fitted model's later batches). The outputs of the two paths
+are compared bit for bit. One JSON line per case; ``--out`` collects them. Not part of any gate.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def synth_forest(te, rng, n_trees, depth, F, B, K, p_split=0.9):
+    """Trees grown level by level (BFS order, as the grower emits them): a node above ``depth`` splits with
+    probability ``p_split`` (the root always), on a random column and bin; gains are log-uniform in [1e-4, 1]."""
+    offs, nodes = [0], []
+    base = 0
+    for _ in range(n_trees):
+        level, tree = 1, []
+        for d in range(depth + 1):
+            split = (rng.random(level) < p_split) & (d < depth)
+            if d == 0:
+                split[:] = depth > 0
+            nd = np.zeros((level, 4), np.int32)
+            first_child = base + sum(len(a) for a in tree) + level
+            rank = np.cumsum(split) - 1
+            nd[:, 0] = np.where(split, rng.integers(0, F, level), 0)
+            nd[:, 1] = np.where(split, rng.integers(0, B - 1, level), 0)
+            nd[:, 2] = np.where(split, first_child + 2 * rank, -1)
+            nd[:, 3] = np.where(split, first_child + 2 * rank + 1, -1)
+            tree.append(nd)
+            level = 2 * int(split.sum())
+            if level == 0:
+                break
+        t = np.concatenate(tree)
+        nodes.append(t)
+        base += len(t)
+        offs.append(base)
+    nodes = np.concatenate(nodes)
+    n = len(nodes)
+    internal = nodes[:, 2] >= 0
+    gain = np.where(internal, np.exp(rng.uniform(np.log(1e-4), 0.0, n)), 0).astype(np.float32)
+    return te.Forest(np.asarray(offs, np.int64), nodes, np.where(internal, rng.integers(0, 2, n), 0).astype(np.uint8),
+                     rng.standard_normal((n, K)).astype(np.float32), gain, np.ones(n, np.float32),
+                     np.zeros(n_trees, np.int32), B - 1)
+
+
+def _event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=3_300_000)
+    ap.add_argument("--cols", default="730,352", help="comma-separated binned column counts")
+    ap.add_argument("--bins", type=int, default=32)
+    ap.add_argument("--multi-trees", type=int, default=50)
+    ap.add_argument("--multi-depth", type=int, default=12)
+    ap.add_argument("--plain-trees", type=int, default=90)
+    ap.add_argument("--plain-depth", type=int, default=10)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from transmogrifai_amd.models import tree_engine as te
+
+    dev = torch.device(a.device)
+    torch.cuda.set_device(dev)
+    rng = np.random.default_rng(7)
+    g = torch.Generator(device=dev).manual_seed(7)
+    rows = torch.randperm(a.rows, generator=g, device=dev)
+    variants = [[(d, mg) for d in (3, 6, 12) for mg in (0.001, 0.01, 0.1)]]
+    lines = []
+    for F in (int(c) for c in a.cols.split(",")):
+        Xb = torch.randint(0, a.bins, (a.rows, F), generator=g, device=dev, dtype=torch.uint8)
+        fm = synth_forest(te, rng, a.multi_trees, a.multi_depth, F, a.bins, 2)
+        fp = synth_forest(te, rng, a.plain_trees, a.plain_depth, F, a.bins, 1)
+        wp = rng.standard_normal(a.plain_trees).astype(np.float32)
+        cases = {
+            "multi": (fm, lambda f: torch.cat([o.reshape(-1) for o in te.forest_predict_multi(
+                f, Xb, [rows], [list(range(f.n_trees))], variants)[0]])),
+            "plain": (fp, lambda f: te.forest_predict(f, Xb, [rows], [list(range(f.n_trees))], wp)[0]),
+        }
+        for name, (forest, score) in cases.items():
+            def fresh():
+                return te.Forest(forest.tree_off, forest.nodes, forest.default_left, forest.value, forest.gain,
+                                 forest.cover, forest.tree_model, forest.missing_bin)
+
+            warm = fresh()
+            real_v1 = te.predict_v1
+
+            def run(v1, f):
+                te.predict_v1 = lambda: v1
+                try:
+                    return _event_ms(lambda: score(f))
+                finally:
+                    te.predict_v1 = real_v1
+
+            paths = {"v1": lambda: run(True, fresh()), "image_cold": lambda: run(False, fresh()),
+                     "image_warm": lambda: run(False, warm)}
+            outs = {k: fn()[1] for k, fn in paths.items()}                       # warm-up
+            times = {k: [] for k in paths}
+            for _ in range(a.runs):
+                for k, fn in paths.items():
+                    times[k].append(fn()[0])
+            res = {"case": name, "rows": a.rows, "F": F, "trees": forest.n_trees, "nodes": len(forest.nodes),
+                   "depth": int(te._node_depth(forest).max()), "K": forest.K,
+                   "variants": len(variants[0]) if name == "multi" else 0,
+                   "gpu": torch.cuda.get_device_name(dev), "runs": a.runs,
+                   "bit_equal": bool(torch.equal(outs["v1"].view(torch.int32), outs["image_cold"].view(torch.int32))
+                                     and torch.equal(outs["v1"].view(torch.int32),
+                                                     outs["image_warm"].view(torch.int32)))}
+            for k, ts in times.items():
+                res[f"{k}_median_ms"] = round(statistics.median(ts), 3)
+                res[f"{k}_runs_ms"] = [round(t, 3) for t in ts]
+            res["v1_over_image_cold"] = round(res["v1_median_ms"] / res["image_cold_median_ms"], 3)
+            res["v1_over_image_warm"] = round(res["v1_median_ms"] / res["image_warm_median_ms"], 3)
+            lines.append(json.dumps(res))
+            print(lines[-1], flush=True)
+        del Xb
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1035,6 +1035,62 @@ def _lds_limit(dev) -> int:
     return 160 * 1024
 
 
+def predict_v1() -> bool:
+    """``TMOG_PREDICT_V1=1``: score with the kernels that read ``nodes`` / ``default_left`` / ``node_mask`` directly
+    instead of the packed node image (the A/B switch; read once per process by the native library)."""
+    return bool(N.hip().tmog_hip_predict_v1())
+
+
+def pack_node_image(nodes: np.ndarray, default_left: np.ndarray, mask: Optional[np.ndarray] = None) -> np.ndarray:
+    """uint32 ``[n, 4]``: the record ``forest_image_kernel`` (tree_kernels.hip) packs for every node,
+    ``(feat | bin << 16 | default_left << 24, variant stop mask, left, right)``: its host twin."""
+    nd = np.asarray(nodes, np.int32).reshape(-1, 4)
+    img = np.zeros((len(nd), 4), np.uint32)
+    img[:, 0] = (nd[:, 0].astype(np.uint32) | (nd[:, 1].astype(np.uint32) << np.uint32(16))
+                 | ((np.asarray(default_left) != 0).astype(np.uint32) << np.uint32(24)))
+    if mask is not None:
+        img[:, 1] = np.asarray(mask, np.uint32)
+    img[:, 2:] = nd[:, 2:].view(np.uint32)
+    return img
+
+
+def image_fits(forest: Forest) -> bool:
+    """A node record holds 16 bits of feature index and 8 bits of split bin."""
+    nd = forest.nodes
+    return len(nd) == 0 or (int(nd[:, 0].min()) >= 0 and int(nd[:, 0].max()) < 65536
+                            and int(nd[:, 1].min()) >= 0 and int(nd[:, 1].max()) < 256)
+
+
+def _scoring_image(forest: Forest, dev, mask_key=None, make_mask=None) -> Optional[torch.Tensor]:
+    """The forest's node image on ``dev`` (int32 ``[n, 4]``), or None when the forest does not fit one (the caller
+    then scores with the direct kernels). Built by ``forest_image_kernel`` and kept on the forest object, per
+    stream like the other device caches here: a fitted model scores every later batch from the same image. It is
+    rebuilt when ``nodes`` or ``default_left`` (or, with variant masks, ``gain`` or the variants: ``mask_key``) is
+    another object than the one it was built from; arrays edited in place are not noticed. ``make_mask()`` gives
+    the uint32 stop mask per node; without it the mask words are 0."""
+    cache = forest.__dict__.setdefault("_images", {})
+    slot = ("plain" if make_mask is None else "multi", str(dev), _stream_key(dev))
+    e = cache.get(slot)
+    src = (forest.nodes, forest.default_left, None if make_mask is None else forest.gain)
+    if e is not None and all(a is b for a, b in zip(e[0], src)) and e[1] == mask_key:
+        return e[2]
+    image = None
+    if image_fits(forest):
+        pk = _Pack(dev)
+        ids = [pk.add(np.ascontiguousarray(forest.nodes)), pk.add(forest.default_left)]
+        if make_mask is not None:
+            ids.append(pk.add(make_mask().view(np.int32)))
+        dv = pk.ship()
+        image = torch.empty((len(forest.nodes), 4), dtype=torch.int32, device=dev)
+        N.check(N.hip().tmog_hip_forest_image(
+            N.ptr(dv[ids[0]]), N.ptr(dv[ids[1]]), N.ptr(dv[ids[2]]) if make_mask is not None else None,
+            len(forest.nodes), N.ptr(image), N.stream(dev)), "forest_image")
+    if len(cache) >= 8:
+        cache.clear()
+    cache[slot] = (src, mask_key, image)
+    return image
+
+
 def forest_predict_multi(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Optional[torch.Tensor]],
                          model_trees: Sequence[Sequence[int]],
                          model_variants: Sequence[Sequence[Tuple[int, float]]]) -> List[List[torch.Tensor]]:
@@ -1076,35 +1132,53 @@ def forest_predict_multi(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[
     # every variant, an internal node those whose min gain exceeds its split gain (fp32 compare)
     # The kernel's depth table ends at _PM_DEPTHS: a deeper max depth is folded into the node bits here (a tree
     # deeper than that variant would otherwise be walked to its grown leaves)
-    mask = np.zeros(len(forest.nodes), np.uint32)
-    leaf = forest.nodes[:, 2] < 0
-    depth = _node_depth(forest) if any(d > _PM_DEPTHS for vs in model_variants for d, _ in vs) else None
-    for m, vs in enumerate(model_variants):
-        sel = np.zeros(len(forest.nodes), bool)
-        for t in model_trees[m]:
-            sel[int(forest.tree_off[t]):int(forest.tree_off[t + 1])] = True
-        bits = np.zeros(len(forest.nodes), np.uint32)
-        for k, (d, g) in enumerate(vs):
-            stop = (forest.gain < np.float32(g)) | leaf
-            if d > _PM_DEPTHS:
-                stop |= depth >= d
-            bits |= stop.astype(np.uint32) << np.uint32(k)
-        mask[sel] = bits[sel]
+    def make_mask() -> np.ndarray:
+        mask = np.zeros(len(forest.nodes), np.uint32)
+        leaf = forest.nodes[:, 2] < 0
+        depth = _node_depth(forest) if any(d > _PM_DEPTHS for vs in model_variants for d, _ in vs) else None
+        for m, vs in enumerate(model_variants):
+            sel = np.zeros(len(forest.nodes), bool)
+            for t in model_trees[m]:
+                sel[int(forest.tree_off[t]):int(forest.tree_off[t + 1])] = True
+            bits = np.zeros(len(forest.nodes), np.uint32)
+            for k, (d, g) in enumerate(vs):
+                stop = (forest.gain < np.float32(g)) | leaf
+                if d > _PM_DEPTHS:
+                    stop |= depth >= d
+                bits |= stop.astype(np.uint32) << np.uint32(k)
+            mask[sel] = bits[sel]
+        return mask
+
+    # the node image carries the mask words: one per (trees, variants) of the call, kept for the next such call
+    image = None if predict_v1() else _scoring_image(
+        forest, dev, (tuple(tuple(int(t) for t in ts) for ts in model_trees),
+                      tuple(tuple((int(d), float(g)) for d, g in vs) for vs in model_variants)), make_mask)
     pk = _Pack(dev)
     ids = [pk.add(forest.tree_off[:-1][order].astype(np.int64)), pk.add(np.ones(len(order), np.float32)),
-           pk.add(np.ascontiguousarray(forest.nodes)), pk.add(forest.default_left),
-           pk.add(np.ascontiguousarray(forest.value, np.float32)), pk.add(mask.view(np.int32))]
+           pk.add(np.ascontiguousarray(forest.value, np.float32))]
+    if image is None:
+        ids += [pk.add(np.ascontiguousarray(forest.nodes)), pk.add(forest.default_left),
+                pk.add(make_mask().view(np.int32))]
     i_v = [pk.add(voff), pk.add(vdep), pk.add(vout), pk.add(mro), pk.add(mto)]
     row_list = torch.cat([(torch.arange(Nrows, device=dev) if r is None else r.to(dev)).to(torch.int32)
                           for r in model_rows])
     dv = pk.ship()
-    t_off, t_w, nodes, dl, lv, gn = (dv[i] for i in ids)
+    t_off, t_w, lv = (dv[i] for i in ids[:3])
     voff_t, vdep_t, vout_t, mro_t, mto_t = (dv[i] for i in i_v)
     out = torch.empty(max(pos, 1), dtype=torch.float32, device=dev)
-    N.check(N.hip().tmog_hip_forest_predict_multi(
-        N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0, N.ptr(mto_t),
-        N.ptr(t_off), N.ptr(t_w), N.ptr(nodes), N.ptr(dl), forest.missing_bin, N.ptr(lv), K, N.ptr(gn), N.ptr(voff_t),
-        N.ptr(vdep_t), N.ptr(vout_t), N.ptr(out), N.stream(dev)), "forest_predict_multi")
+    if image is not None:
+        N.check(N.hip().tmog_hip_forest_predict_multi_image(
+            N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
+            N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(image), forest.missing_bin, N.ptr(lv), K, N.ptr(voff_t),
+            N.ptr(vdep_t), N.ptr(vout_t), max((len(v) for v in model_variants), default=0), N.ptr(out),
+            N.stream(dev)), "forest_predict_multi_image")
+    else:
+        nodes, dl, gn = (dv[i] for i in ids[3:])
+        N.check(N.hip().tmog_hip_forest_predict_multi(
+            N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
+            N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(nodes), N.ptr(dl), forest.missing_bin, N.ptr(lv), K,
+            N.ptr(gn), N.ptr(voff_t), N.ptr(vdep_t), N.ptr(vout_t), N.ptr(out), N.stream(dev)),
+            "forest_predict_multi")
     res = []
     for m, vs in enumerate(model_variants):
         res.append([out[int(vout[int(voff[m]) + k]):int(vout[int(voff[m]) + k]) + counts[m] * K].view(counts[m], K)
@@ -1130,10 +1204,12 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
     mto = np.zeros(len(model_trees) + 1, np.int64)
     mto[1:] = np.cumsum([len(ts) for ts in model_trees])
     tw = np.ones(forest.n_trees, np.float32) if tree_weight is None else np.asarray(tree_weight, np.float32)
+    image = None if dev.type != "cuda" or predict_v1() else _scoring_image(forest, dev)
     pk = _Pack(dev)
     ids = [pk.add(forest.tree_off[:-1][order].astype(np.int64)), pk.add(tw[order]),
-           pk.add(np.ascontiguousarray(forest.nodes)), pk.add(forest.default_left),
            pk.add(np.ascontiguousarray(forest.value, np.float32))]
+    if image is None:
+        ids += [pk.add(np.ascontiguousarray(forest.nodes)), pk.add(forest.default_left)]
     counts = [Nrows if r is None else int(r.numel()) for r in model_rows]
     mro = np.zeros(len(model_rows) + 1, np.int64)
     mro[1:] = np.cumsum(counts)
@@ -1146,7 +1222,8 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
                               for r in model_rows])
     i_mro, i_mto = pk.add(mro), pk.add(mto)
     dv = pk.ship()
-    t_off, t_w, nodes, dl, lv = (dv[i] for i in ids)
+    t_off, t_w, lv = (dv[i] for i in ids[:3])
+    nodes, dl = (dv[i] for i in ids[3:]) if image is None else (None, None)
     mro_t, mto_t = dv[i_mro], dv[i_mto]
     out = torch.zeros(int(mro[-1]), K, dtype=torch.float32, device=dev)
     if dev.type == "cuda":
@@ -1155,10 +1232,16 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
             kc = min(8, K - c0)
             lvc = lv if kc == K else lv[:, c0:c0 + kc].contiguous()
             oc = out if kc == K else torch.empty(int(mro[-1]), kc, dtype=torch.float32, device=dev)
-            N.check(N.hip().tmog_hip_forest_predict(
-                N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
-                N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(nodes), N.ptr(dl), forest.missing_bin, N.ptr(lvc), kc,
-                N.ptr(oc), N.stream(dev)), "forest_predict")
+            if image is not None:
+                N.check(N.hip().tmog_hip_forest_predict_image(
+                    N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
+                    N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(image), forest.missing_bin, N.ptr(lvc), kc,
+                    N.ptr(oc), N.stream(dev)), "forest_predict_image")
+            else:
+                N.check(N.hip().tmog_hip_forest_predict(
+                    N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
+                    N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(nodes), N.ptr(dl), forest.missing_bin, N.ptr(lvc),
+                    kc, N.ptr(oc), N.stream(dev)), "forest_predict")
             if kc != K:
                 out[:, c0:c0 + kc] = oc
     else:

@@ -229,6 +229,21 @@ int tmog_hip_forest_predict(const uint8_t* Xb, int F, int n_models, const int64_
                             const int64_t* tree_off, const float* tree_weight, const int32_t* nodes,
                             const uint8_t* default_left, int missing_bin, const float* leaf_value, int K, float* out,
                             hipStream_t stream);
+// The same scoring over a packed node image (16 bytes per node: feat | bin << 16 | default_left << 24, variant stop
+// mask, left, right) that tmog_hip_forest_image builds once per forest; tmog_hip_predict_v1 is TMOG_PREDICT_V1=1.
+int tmog_hip_predict_v1();
+int tmog_hip_forest_image(const int32_t* nodes, const uint8_t* default_left, const uint32_t* node_mask, int64_t n,
+                          int32_t* image, hipStream_t stream);
+int tmog_hip_forest_predict_multi_image(const uint8_t* Xb, int F, int n_models, const int64_t* model_row_off,
+                                        const int32_t* row_list, int64_t max_rows, const int64_t* model_tree_off,
+                                        const int64_t* tree_off, const float* tree_weight, const int32_t* image,
+                                        int missing_bin, const float* leaf_value, int K, const int32_t* var_off,
+                                        const int32_t* var_depth, const int64_t* var_out_off, int max_variants,
+                                        float* out, hipStream_t stream);
+int tmog_hip_forest_predict_image(const uint8_t* Xb, int F, int n_models, const int64_t* model_row_off,
+                                  const int32_t* row_list, int64_t max_rows, const int64_t* model_tree_off,
+                                  const int64_t* tree_off, const float* tree_weight, const int32_t* image,
+                                  int missing_bin, const float* leaf_value, int K, float* out, hipStream_t stream);
 
 // ---- hip/staged_eval_kernels.hip: the contract of tmog_forest_staged_eval_cpu (common/tmog_abi.h); slab holds
 // ceil(n / TMOG_EVAL_BLOCK) x S doubles, the per-workgroup partial sums that values[] is reduced from in a fixed order
