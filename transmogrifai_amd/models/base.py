@@ -140,6 +140,12 @@ class Learner:
         raise NotImplementedError(f"{self.name} has no exact SHAP attributions; RecordInsightsLOCO explains "
                                   "any model")
 
+    def loco_scores(self, state, X: torch.Tensor, groups=None, rows=None, context=None):
+        """Exact leave-one-column-out scores without rescoring (tree learners: path perturbation):
+        ``(base [n, C'], perturbed [n, U + G, C'], used)``, the score columns ``RecordInsightsLOCO`` ranks by."""
+        raise NotImplementedError(f"{self.name} has no path-perturbation LOCO; RecordInsightsLOCO's rescore mode "
+                                  "explains any model")
+
     def state_to_json(self, state: dict) -> dict:
         from ..utils.serde import encode
         return encode(state)

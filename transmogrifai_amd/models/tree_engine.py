@@ -1529,3 +1529,132 @@ def forest_shap(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor] =
         fp.p_val.ctypes.data, KV, bias.ctypes.data, fp.e_feat.ctypes.data, fp.e_rng.ctypes.data,
         fp.e_z.ctypes.data, bo.ctypes.data, fp.missing_bin, C, fp.scale, N.ptr(out)), "forest_shap_cpu")
     return out, used64
+
+
+# ------------------------------------------------------------------------------------- path-perturbation LOCO
+@dataclass
+class ForestLoco:
+    """What :func:`forest_loco` reads of one forest / weights / output columns (:func:`forest_loco_plan`)."""
+    used: np.ndarray                # int32 [U]   distinct split columns, sorted
+    nodes: np.ndarray               # int32 [n, 4] (slot u, bin | default_left << 16, left, right), left < 0 => leaf
+    tree_off: np.ndarray            # int64 [T + 1]
+    value: np.ndarray               # float32 [n, KV]
+    tree_weight: np.ndarray         # float32 [T]
+    tree_out: np.ndarray            # int32 [T]   first output column of the tree
+    n_out: int                      # output columns the trees need
+    S: float                        # sum_t |w_t| max_node |value_t|: the magnitude bound of the base sum
+    missing_bin: int = -1
+    _dev: dict = field(default_factory=dict, repr=False)
+
+    @property
+    def scale(self) -> float:
+        """The power of two with ``S * scale < 2^61``: a delta slot's partial sums stay within ``2 S``
+        (``ops/csrc/hip/loco_kernels.hip`` has the bound), so the int64 fixed-point sums cannot overflow."""
+        if not (self.S > 0 and math.isfinite(self.S)):
+            return 1.0
+        return 2.0 ** max(-1000, min(1000, 61 - math.frexp(self.S)[1]))
+
+    def on(self, dev):
+        """The arrays the kernel reads, resident on ``dev`` (shipped once)."""
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (
+                self.used, self.tree_off, self.nodes, self.value, self.tree_weight, self.tree_out))
+        return self._dev[key]
+
+
+def forest_loco_plan(forest: Forest, tree_weight: Optional[np.ndarray] = None,
+                     tree_out: Optional[np.ndarray] = None) -> ForestLoco:
+    """The node records of :func:`forest_loco`: the forest's nodes with each split column replaced by its index in
+    the sorted distinct split columns and the default direction folded into the bin word. Tree weights are taken
+    as fp32, as the predictors take them."""
+    T = forest.n_trees
+    tw = np.ones(T, np.float32) if tree_weight is None else np.ascontiguousarray(tree_weight, np.float32)
+    tout = np.zeros(T, np.int32) if tree_out is None else np.ascontiguousarray(tree_out, np.int32)
+    if tw.shape != (T,) or tout.shape != (T,):
+        raise ValueError("tree_weight / tree_out must have one entry per tree")
+    if T and int(tout.min()) < 0:
+        raise ValueError("tree_out must not be negative")
+    nd = forest.nodes
+    internal = nd[:, 2] >= 0
+    used = np.unique(nd[internal, 0]).astype(np.int32)
+    if internal.any() and (int(nd[internal, 1].min()) < 0 or int(nd[internal, 1].max()) > 0xFFFF):
+        raise ValueError("split bins must fit 16 bits")
+    nodes = np.zeros((len(nd), 4), np.int32)
+    nodes[:, 0] = np.where(internal, np.searchsorted(used, nd[:, 0]), 0)
+    nodes[:, 1] = np.where(internal, nd[:, 1] | (forest.default_left.astype(np.int32) != 0) << 16, 0)
+    nodes[:, 2] = np.where(internal, nd[:, 2], -1)
+    nodes[:, 3] = np.where(internal, nd[:, 3], -1)
+    value = np.ascontiguousarray(forest.value, np.float32).reshape(len(nd), -1)
+    S = 0.0
+    for t in range(T):
+        a, b = int(forest.tree_off[t]), int(forest.tree_off[t + 1])
+        if b > a and value[a:b].size:
+            S += abs(float(tw[t])) * float(np.abs(value[a:b]).max())
+    n_out = (int(tout.max()) if T else 0) + forest.K
+    return ForestLoco(used, nodes, np.ascontiguousarray(forest.tree_off, np.int64), value, tw, tout, n_out, float(S),
+                      int(forest.missing_bin))
+
+
+def forest_loco(forest: Forest, Xb: torch.Tensor, zero_bins, rows: Optional[torch.Tensor] = None,
+                groups: Optional[Sequence] = None, tree_weight: Optional[np.ndarray] = None,
+                tree_out: Optional[np.ndarray] = None, n_out: Optional[int] = None,
+                plan: Optional[ForestLoco] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """Exact leave-one-column-out sums of the forest's ``tree_weight``-weighted leaf-value sum on rows ``rows``
+    (None = all) of the binned matrix, by perturbing tree paths instead of rescoring rows:
+    ``(out float64 [n, U + G + 1, C], used int64 [U])``. ``zero_bins`` (uint8 ``[F]``) is the bin the value 0.0 falls
+    into per column; ``groups`` an optional list of G disjoint arrays of column ids, each zeroed as a whole (members
+    the forest does not split on are allowed). Slot ``u < U`` is the sum with column ``used[u]`` replaced by its zero
+    bin minus the unperturbed sum (exactly 0.0 when nothing changes), slot ``U + g`` the same with every column of
+    group ``g`` replaced at once, the last slot the unperturbed sum. Tree ``t``'s ``K`` leaf values go to columns
+    ``tree_out[t] .. tree_out[t] + K - 1`` of ``C = n_out``. Device matrices run ``tmog_hip_forest_loco``; host
+    matrices, and a launch whose one-row tile is beyond the LDS limit, run the host twin -- both sum in the same
+    int64 fixed point, so they agree bit for bit. ``plan``: the prepared :func:`forest_loco_plan` of the same
+    forest / weights / columns (callers cache it)."""
+    lp = plan if plan is not None else forest_loco_plan(forest, tree_weight, tree_out)
+    C = int(n_out) if n_out is not None else lp.n_out
+    if C < lp.n_out:
+        raise ValueError(f"n_out = {C} but the trees write {lp.n_out} columns")
+    dev = Xb.device
+    Xb = Xb.contiguous()
+    if Xb.dtype != torch.uint8 or Xb.dim() != 2:
+        raise ValueError("Xb must be a uint8 [N, F] matrix")
+    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
+    if lp.used.size and int(lp.used[-1]) >= F:
+        raise ValueError(f"the forest splits on column {int(lp.used[-1])}, the matrix has {F}")
+    zb = zero_bins.cpu().numpy() if isinstance(zero_bins, torch.Tensor) else np.asarray(zero_bins)
+    zb = zb.reshape(-1).astype(np.int32)
+    if zb.size != F:
+        raise ValueError(f"zero_bins has {zb.size} entries, the matrix {F} columns")
+    U, T, KV = int(lp.used.size), int(lp.tree_weight.size), int(lp.value.shape[1])
+    glist = [np.asarray(g.cpu() if isinstance(g, torch.Tensor) else g, np.int64).reshape(-1) for g in (groups or [])]
+    G = len(glist)
+    group_of = np.full(F, -1, np.int32)
+    for g, cols in enumerate(glist):
+        if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= F):
+            raise ValueError(f"group {g} names a column outside the matrix")
+        if (group_of[cols] >= 0).any() or np.unique(cols).size != cols.size:
+            raise ValueError("groups must be disjoint")
+        group_of[cols] = g
+    meta = ((zb[lp.used] & 0xFF) | ((group_of[lp.used] + 1) << 8)).astype(np.int32)
+    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
+    n = Nrows if rows is None else int(row_list.numel())
+    used64 = lp.used.astype(np.int64)
+    out = torch.empty(n, U + G + 1, C, dtype=torch.float64, device=dev)
+    if dev.type == "cuda":
+        d = lp.on(dev)
+        meta_d = _const_tensor(meta, dev)
+        rc = N.hip().tmog_hip_forest_loco(
+            N.ptr(Xb), F, n, N.ptr(row_list), U, N.ptr(d[0]), N.ptr(meta_d), G, T, N.ptr(d[1]), N.ptr(d[2]),
+            int(lp.nodes.shape[0]), N.ptr(d[3]), KV, N.ptr(d[4]), N.ptr(d[5]), lp.missing_bin, C, lp.scale,
+            N.ptr(out), N.stream(dev))
+        if rc == -3:                 # one row's tile beyond the LDS limit
+            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
+            return forest_loco(forest, sub.cpu(), zb, None, glist, n_out=C, plan=lp)[0].to(dev), used64
+        N.check(rc, "forest_loco")
+        return out, used64
+    N.check(N.host().tmog_forest_loco_cpu(
+        N.ptr(Xb), F, n, N.ptr(row_list), U, lp.used.ctypes.data, meta.ctypes.data, G, T, lp.tree_off.ctypes.data,
+        lp.nodes.ctypes.data, lp.value.ctypes.data, KV, lp.tree_weight.ctypes.data, lp.tree_out.ctypes.data,
+        lp.missing_bin, C, lp.scale, N.ptr(out)), "forest_loco_cpu")
+    return out, used64

@@ -107,6 +107,28 @@ def _ctx(X, context):
     return TreeContext(X)
 
 
+def _zero_bins(X: torch.Tensor, spec: BinSpec) -> torch.Tensor:
+    """uint8 ``[F]``: the bin of the value 0.0 per column, from the same ``quantize`` call (dtype, device) that bins
+    ``X`` -- what a rescored copy of a row with that column zeroed would hold."""
+    return quantize(torch.zeros(1, int(X.shape[1]), dtype=X.dtype, device=X.device), spec)[0]
+
+
+def _loco_outputs(outputs, out: torch.Tensor, base_margin: float):
+    """``TE.forest_loco``'s sums ``[n, U + G + 1, C]`` through a learner's ``outputs(sums [k, C]) -> (prediction,
+    raw, probability)``: ``(base [n, C'], perturbed [n, U + G, C'])``, base + delta formed in fp64; the score columns
+    are the probabilities if the learner has them, else the prediction as one column."""
+    n, m, C = int(out.shape[0]), int(out.shape[1]) - 1, int(out.shape[2])
+
+    def scores(s):
+        pred, _, prob = outputs(s)
+        return (prob if prob.shape[1] > 0 else pred.reshape(-1, 1)).to(torch.float64)
+
+    base_sum = out[:, -1, :] + base_margin
+    base = scores(base_sum)
+    pert = scores((base_sum[:, None, :] + out[:, :-1, :]).reshape(n * m, C))
+    return base, pert.reshape(n, m, int(base.shape[1]))
+
+
 def _subset_size(strategy, F: int, classification: bool, num_trees: int) -> int:
     s = str(strategy).lower()
     if s == "auto":
@@ -370,6 +392,19 @@ class _ForestLearner(Learner):
                 w = np.full(forest.n_trees, 1.0 / max(1, int(state.get("num_trees", 1))))
             state["_shap_paths"] = TE.forest_paths(forest, w)
         return TE.forest_shap(forest, Xb, rows, paths=state["_shap_paths"])
+
+    def loco_scores(self, state, X, groups=None, rows=None, context=None):
+        """Exact LOCO scores by tree-path perturbation (``TE.forest_loco``): ``(base [n, C'], perturbed
+        [n, U + G, C'], used)`` -- the probabilities (a regressor: the prediction, one column) of every record
+        as it is, and with each used column / each column group of ``groups`` at zero. The raw class-vote sums
+        are perturbed (a regressor's too: ``_outputs`` divides by the tree count)."""
+        forest, Xb = self._binned(state, X, context)
+        if "_loco_plan" not in state:
+            state["_loco_plan"] = TE.forest_loco_plan(forest)
+        out, used = TE.forest_loco(forest, Xb, _zero_bins(X, self._forest(state)[1]), rows, groups,
+                                   plan=state["_loco_plan"])
+        base, pert = _loco_outputs(lambda raw: self._outputs(state, raw), out, 0.0)
+        return base, pert, used
 
     def predict_batch(self, states, X, rows, context=None):
         if not states:
@@ -677,6 +712,24 @@ class _BoostLearner(Learner):
         if self.classification and not multi:
             phi = torch.cat([-phi, phi], 2)
         return phi, used
+
+    def loco_scores(self, state, X, groups=None, rows=None, context=None):
+        """Exact LOCO scores by tree-path perturbation (``TE.forest_loco``): ``(base [n, C'], perturbed
+        [n, U + G, C'], used)`` -- the probabilities (a regressor: the prediction, one column) of every record
+        as it is, and with each used column / each column group of ``groups`` at zero. The margin is perturbed
+        (a multiclass model's K margins: tree ``t`` belongs to class ``t % K``), ``base_margin`` added as
+        :meth:`margin` adds it."""
+        forest, Xb = self._binned_for(state, X, context)
+        multi = state.get("objective") in MULTI_OBJECTIVES
+        K = int(state["n_classes"]) if multi else 1
+        if "_loco_plan" not in state:
+            state["_loco_plan"] = TE.forest_loco_plan(forest, np.asarray(state["tree_weights"], np.float32),
+                                                      np.arange(forest.n_trees) % K if multi else None)
+        out, used = TE.forest_loco(forest, Xb, _zero_bins(X, self._forest(state)[1]), rows, groups, n_out=K,
+                                   plan=state["_loco_plan"])
+        base, pert = _loco_outputs(lambda m: self._outputs(state, m if multi else m[:, 0]), out,
+                                   float(state.get("base_margin", 0.0)))
+        return base, pert, used
 
     def predict_batch(self, states, X, rows, context=None):
         return [self._outputs(s, self.margin(s, X, r, context)) for s, r in zip(states, rows)]

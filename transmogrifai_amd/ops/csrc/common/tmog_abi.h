@@ -183,6 +183,19 @@ int tmog_murmur3_batch(const uint8_t* bytes, const int64_t* offsets, int64_t n, 
 int tmog_hash_index_batch(const uint8_t* bytes, const int64_t* offsets, int64_t n, int32_t seed, int32_t num_features,
                           int32_t* out);
 
+// ---- host/loco_cpu.cpp
+// Exact leave-one-column-out sums by tree-path perturbation, out[i][U + G + 1][C] (fp64) for rows row_list[0 .. n)
+// (null: rows 0 .. n-1) of Xb [.][F]. nodes is the forest's node array with the split column replaced by its slot u
+// in used[U] and the default direction folded in: (u, bin | default_left << 16, left, right), left < 0 a leaf;
+// slot_meta[u] = zero bin of used[u] | (group + 1) << 8 (group -1: none, G groups). Tree t's KV leaf values, times
+// tree_weight[t], go to columns tree_out[t] + c of C. Slot u: the sum with column used[u] at its zero bin minus the
+// unperturbed sum; slot U + g: the same with every column of group g replaced; the last slot: the unperturbed sum.
+// scale: the power of two of the int64 fixed-point accumulation (hip/loco_kernels.hip has the bound).
+int tmog_forest_loco_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
+                         const int32_t* slot_meta, int G, int64_t T, const int64_t* tree_off, const int32_t* nodes,
+                         const float* value, int KV, const float* tree_weight, const int32_t* tree_out,
+                         int missing_bin, int C, double scale, double* out);
+
 // ---- host/streaming_histogram.cpp
 void* tmog_shist_new(int max_bins, int max_spool, int64_t round_to);
 void tmog_shist_free(void* h);

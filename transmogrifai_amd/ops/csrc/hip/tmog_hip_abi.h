@@ -80,6 +80,13 @@ int tmog_hip_owlqn_candidate(const double* U, const double* D, const double* xi,
                              const double* alpha, int d1, int P, double* cand, double* l1t, double* dd,
                              hipStream_t stream);
 
+// ---- hip/loco_kernels.hip
+int tmog_hip_forest_loco(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
+                         const int32_t* slot_meta, int G, int64_t T, const int64_t* tree_off, const int32_t* nodes,
+                         int64_t n_nodes, const float* value, int KV, const float* tree_weight,
+                         const int32_t* tree_out, int missing_bin, int C, double scale, double* out,
+                         hipStream_t stream);
+
 // ---- hip/metric_kernels.hip
 int tmog_hip_binary_areas(const void* s, int is_f64, const int64_t* idx, int64_t n, int J, const uint8_t* lab,
                           double* out_pr, double* out_roc, hipStream_t stream);

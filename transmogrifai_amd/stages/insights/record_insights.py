@@ -11,6 +11,9 @@ column) perturbation becomes one row of a perturbed batch scored by the model's 
 (for linear models the batch is never materialized: the perturbed margin is ``m_i - w_j x_ij``, an
 elementwise [rows, d] tensor op); top-K selection per record is ``torch.topk`` over the
 [rows, candidates] score-change matrix. Only the final ``TextMap`` strings are built on the host.
+For tree models ``perturbation="paths"`` replaces the perturbed batches by exact path perturbation
+(``tree_engine.forest_loco``, HIP kernel ``ops/csrc/hip/loco_kernels.hip``): a zeroed column can change a tree's
+answer only where it is tested on the record's own path, so only those path suffixes are walked again.
 
 Beyond the reference: ``RecordInsightsSHAP`` explains tree models with exact path-dependent TreeSHAP
 (``tree_engine.forest_shap``, HIP kernel ``ops/csrc/hip/shap_kernels.hip``) instead of perturbing columns.
@@ -128,7 +131,9 @@ class RecordInsightsLOCO(UnaryTransformer):
     """Unary (OPVector -> TextMap) transformer wrapping a fitted prediction model stage."""
     operation_name = "recordInsightsLOCO"
     output_type = T.TextMap
-    _defaults = {"top_k": 20, "top_k_strategy": "abs", "vector_aggregation_strategy": "Avg"}
+    _defaults = {"top_k": 20, "top_k_strategy": "abs", "vector_aggregation_strategy": "Avg",
+                 "perturbation": "rescore"}
+    PERTURBATIONS = ("rescore", "paths", "auto")
 
     def __init__(self, model=None, uid=None, **kw):
         super().__init__(None, uid=uid, **kw)
@@ -150,6 +155,33 @@ class RecordInsightsLOCO(UnaryTransformer):
         else:
             s = pred.reshape(-1, 1)
         return s.to(torch.float64), pred.reshape(-1)
+
+    def _use_paths(self) -> bool:
+        """``perturbation``: ``rescore`` (default) scores one perturbed copy of the record per non-zero column;
+        ``paths`` asks the learner for exact LOCO scores by tree-path perturbation (``Learner.loco_scores``, tree
+        learners: ``tree_engine.forest_loco``) and is an error for a learner without them; ``auto`` takes paths
+        where the learner has them and rescores otherwise."""
+        mode = self.params.get("perturbation", "rescore")
+        if mode not in self.PERTURBATIONS:
+            raise ValueError(f"perturbation must be one of {self.PERTURBATIONS}, got {mode!r}")
+        if mode == "rescore":
+            return False
+        from ...models.base import Learner
+        learner = self._learner_state()[0]
+        has = getattr(type(learner), "loco_scores", Learner.loco_scores) is not Learner.loco_scores
+        if mode == "paths" and not has:
+            raise ValueError(f"perturbation='paths' needs a tree learner with loco_scores, "
+                             f"{getattr(learner, 'name', type(learner).__name__)} has none (use 'rescore' or 'auto')")
+        return has
+
+    def _paths_diffs(self, X: torch.Tensor, gcols):
+        """Score changes from the learner's path-perturbation LOCO: (per used column [n, U, C], per column group
+        [n, G, C], used columns [U])."""
+        learner, state = self._learner_state()
+        base, pert, used = learner.loco_scores(state, X, groups=[g.cpu().numpy() for g in gcols])
+        diff = base[:, None, :] - pert
+        U = len(used)
+        return diff[:, :U], diff[:, U:], torch.as_tensor(np.asarray(used, np.int64), device=X.device)
 
     # -- groups of columns aggregated as one insight (text hashes, date unit circles)
     def _groups(self, hist: List[dict]):
@@ -191,15 +223,38 @@ class RecordInsightsLOCO(UnaryTransformer):
         return (cand_of_col.to(device), torch.as_tensor(gsize, dtype=torch.float64, device=device),
                 plain_col.to(device), gcols)
 
+    def _rescore_changes(self, X, nz, base, cand_of_col, gsize):
+        """``[n * m, C]`` score changes of the rescore mode: one perturbed copy per (record, non-zero column),
+        scored in bounded chunks, its change added to the column's candidate (divided by the group size)."""
+        n, d = X.shape
+        dev = X.device
+        m, C = int(gsize.numel()), base.shape[1]
+        rows, cols = torch.nonzero(nz, as_tuple=True)
+        V = torch.zeros(n * m, C, dtype=torch.float64, device=dev)
+        cand = cand_of_col[cols]
+        step = max(1, self.chunk_elems // max(d, 1))
+        ar = torch.arange(min(step, rows.numel()), device=dev)
+        for a in range(0, rows.numel(), step):
+            r, c = rows[a:a + step], cols[a:a + step]
+            Xp = X.index_select(0, r)
+            Xp[ar[:r.numel()], c] = 0
+            s, _ = self._scores(Xp)
+            ca = cand[a:a + step]
+            V.index_add_(0, r * m + ca, (base.index_select(0, r) - s) / gsize[ca][:, None])
+        return V
+
     def _loco_block(self, X: torch.Tensor, hist: List[dict], plan=None):
         """Top-K score changes of one block of records, all on the device: (column [n, K] (-1 = no
         insight), diffs [n, K, C]). Every (record, non-zero column) perturbation is one row of a perturbed
         batch; its score change is scattered into the record's candidate (the column itself, or its
         text / date group: ``Avg`` divides the group sum by the group size, ``LeaveOutVector`` re-scores
         the record with the whole group zeroed), then the top-K positive and negative candidates are
-        merged and ordered per record by one stable sort (``RecordInsightsLOCO.scala:246-273``)."""
+        merged and ordered per record by one stable sort (``RecordInsightsLOCO.scala:246-273``). In paths mode
+        (:meth:`_use_paths`) the score changes come from ``Learner.loco_scores`` instead of perturbed batches --
+        a column the trees do not split on changes nothing -- and everything after them is the same code."""
         n, d = X.shape
         dev = X.device
+        paths = self._use_paths()
         base, pred_cls = self._scores(X)
         C = base.shape[1]
         if C == 0:
@@ -220,20 +275,13 @@ class RecordInsightsLOCO(UnaryTransformer):
             return (torch.full((n, K), -1, dtype=torch.long, device=dev),
                     torch.zeros(n, K, C, dtype=torch.float64, device=dev))
         nz = X != 0
-        rows, cols = torch.nonzero(nz, as_tuple=True)
-        V = torch.zeros(n * m, C, dtype=torch.float64, device=dev)
-        cand = cand_of_col[cols]
-        # one perturbed copy per (record, non-zero column), scored in bounded chunks
-        step = max(1, self.chunk_elems // max(d, 1))
-        ar = torch.arange(min(step, rows.numel()), device=dev)
-        for a in range(0, rows.numel(), step):
-            r, c = rows[a:a + step], cols[a:a + step]
-            Xp = X.index_select(0, r)
-            Xp[ar[:r.numel()], c] = 0
-            s, _ = self._scores(Xp)
-            ca = cand[a:a + step]
-            V.index_add_(0, r * m + ca, (base.index_select(0, r) - s) / gsize[ca][:, None])
-        V = V.view(n, m, C)
+        if paths:
+            col_diff, group_diff, used = self._paths_diffs(X, gcols)
+            cu = cand_of_col[used]
+            V = torch.zeros(n, m, C, dtype=torch.float64, device=dev)
+            V.index_add_(1, cu, col_diff / gsize[cu][None, :, None])
+        else:
+            V = self._rescore_changes(X, nz, base, cand_of_col, gsize).view(n, m, C)
         Cc = plain_col[None, :].expand(n, m).clone()
         n_plain = m - len(gcols)
         leave_out = self.params["vector_aggregation_strategy"] != "Avg"
@@ -242,7 +290,9 @@ class RecordInsightsLOCO(UnaryTransformer):
             has = active.any(1)
             Cc[:, n_plain + g] = torch.where(has, gct[active.to(torch.int8).argmax(1)], torch.full_like(has, -1,
                                                                                                     dtype=torch.long))
-            if leave_out:       # LeaveOutVector: zero every active column of the group at once
+            if leave_out and paths:
+                V[:, n_plain + g] = torch.where(has[:, None], group_diff[:, g], torch.zeros_like(base))
+            elif leave_out:     # LeaveOutVector: zero every active column of the group at once
                 Xp = X.clone()
                 Xp[:, gct] = 0
                 s, _ = self._scores(Xp)
@@ -292,12 +342,14 @@ class RecordInsightsLOCO(UnaryTransformer):
     def ctor_args(self):
         from ...workflow.io import stage_to_json
         return {"model": stage_to_json(self.model) if self.model is not None else None,
-                "histories": self.histories}
+                "histories": self.histories, "perturbation": self.params.get("perturbation", "rescore")}
 
     def load_ctor_args(self, a):
         from ...workflow.io import _build_stage
         self.model = _build_stage(a["model"]) if a.get("model") else None
         self.histories = a.get("histories")
+        if a.get("perturbation") is not None:
+            self.params["perturbation"] = a["perturbation"]
 
 
 # ---------------------------------------------------------------------------------------------- SHAP
@@ -311,7 +363,7 @@ class RecordInsightsSHAP(RecordInsightsLOCO):
     SHAP is additive, so there is no aggregation strategy -- reported under its first active column (its
     first split column when the record has none). Top-K selection is LOCO's, by the same score column."""
     operation_name = "recordInsightsSHAP"
-    _defaults = {"top_k": 20, "top_k_strategy": "abs"}
+    _defaults = {"top_k": 20, "top_k_strategy": "abs", "perturbation": "rescore"}    # perturbation: ignored
 
     def _shap(self, X: torch.Tensor, context=None):
         learner, state = self._learner_state()
