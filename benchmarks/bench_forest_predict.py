@@ -1,4 +1,4 @@
-"""Forest scoring: the node-image kernels against the kernels they replace (``TMOG_PREDICT_V1=1``).
+"""Forest scoring: the packed node image against the direct node source (``TMOG_PREDICT_V1=1``) of one kernel body.
 
 Synthetic binned rows (``--rows`` x F uint8) and synthetic forests, scored through ``tree_engine.forest_predict`` /
 ``forest_predict_multi`` on listed rows (a shuffled held-out fold), the way cross-validation calls them:
@@ -9,9 +9,10 @@ Synthetic binned rows (``--rows`` x F uint8) and synthetic forests, scored throu
   (``forest_predict_lds_kernel`` at F <= 512, ``forest_predict_kernel`` above).
 
 Each case is timed with device events in one process, the two paths alternating, ``--runs`` times after one warm-up
-each. ``v1`` is the old path, ``image_cold`` the new one on a forest object that has no image yet (the image build
-and its upload are inside the timed region, as in a cross-validation that scores every forest once), ``image_warm``
-the new one on a forest that has been scored before (a fitted model's later batches). The outputs of the two paths
+each. ``v1`` is the direct node source (the kernels read ``nodes`` / ``default_left`` / ``node_mask``), ``image_cold``
+the image on a forest object that has none yet (the image build and its upload are inside the timed region, as in a
+cross-validation that scores every forest once), ``image_warm`` the image on a forest that has been scored before (a
+fitted model's later batches). The outputs of the two paths
 are compared bit for bit. One JSON line per case; ``--out`` collects them. Not part of any gate.
 """
 from __future__ import annotations

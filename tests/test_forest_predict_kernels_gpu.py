@@ -1,9 +1,14 @@
 """Kernel-level oracle tests of the forest scoring kernels in ``ops/csrc/hip/tree_kernels.hip``:
-``forest_predict_lds_kernel`` (F <= 512), ``forest_predict_kernel`` (the F > 512 fallback) and
-``forest_predict_multi_kernel<1|2|4|8>``, on hand-built forests (tests/forest_predict_oracle.py, validated against the
+``forest_predict_lds_kernel<NS>`` (F <= 512), ``forest_predict_kernel<NS>`` (the F > 512 fallback) and
+``forest_predict_multi_kernel<NS, 1|2|4|8, VKP>``, each over both node sources ``NS`` (``ImageNodes``, the packed node
+image, and ``DirectNodes``, which ``TMOG_PREDICT_V1=1`` selects: the autouse fixture ``node_source`` patches
+``tree_engine.predict_v1``), on hand-built forests (tests/forest_predict_oracle.py, validated against the
 host twin in tests/test_forest_predict_oracle.py). Each case is named after the path it forces. Exact-regime cases
 compare with equality, rounded-regime cases with the oracle's per-output bound ``(T + 2) 2^-24 sum |w v|``; the
-write-guard cases go through the C entry points with sentinel-filled buffers."""
+write-guard cases go through the direct C entry points with sentinel-filled buffers, whatever the fixture says, so
+they run once."""
+import types
+
 import numpy as np
 import pytest
 import torch
@@ -14,6 +19,18 @@ from transmogrifai_amd.ops._native import ABI_CONSTS
 
 PM_VK = ABI_CONSTS["TMOG_PM_VK"]
 SENT = np.float32(-1.5e30)
+
+
+DIRECT = "_direct_source"      # suffix of the copies at the end of the module that run on the direct node source
+
+
+@pytest.fixture(autouse=True)
+def node_source(request, monkeypatch):
+    """Every oracle case of the module runs on both node sources, switched the way ``TMOG_PREDICT_V1`` does: under its
+    own name on the image, and as ``<name>_direct_source`` (made at the end of the module) on the direct source."""
+    source = "direct" if request.node.originalname.endswith(DIRECT) else "image"
+    monkeypatch.setattr(te, "predict_v1", lambda: source == "direct")
+    return source
 
 
 def _loaded():
@@ -471,3 +488,17 @@ def test_launcher_guards_refuse_without_a_launch():
     torch.cuda.synchronize()
     assert (buf.cpu().numpy() == SENT).all()
     assert _loaded()
+
+
+
+# ===================================================================== the oracle cases again, on the direct source
+# A copy of every test above that scores through ``tree_engine`` (the three raw-entry tests call the direct entries
+# themselves and run once), with its marks and parameters, under the name the fixture looks for.
+RAW_ENTRY = ("test_predict_writes_exactly_its_rows", "test_multi_writes_exactly_its_variant_regions",
+             "test_launcher_guards_refuse_without_a_launch")
+for _name, _test in list(globals().items()):
+    if _name.startswith("test_") and _name not in RAW_ENTRY:
+        _copy = types.FunctionType(_test.__code__, globals(), _name + DIRECT, _test.__defaults__, _test.__closure__)
+        _copy.__dict__.update(_test.__dict__)
+        _copy.__doc__ = _test.__doc__
+        globals()[_name + DIRECT] = _copy

@@ -1,10 +1,15 @@
-"""The node-image scoring kernels of ``ops/csrc/hip/tree_kernels.hip`` (``forest_predict_lds_img_kernel``,
-``forest_predict_img_kernel``, ``forest_predict_multi_img_kernel<KT, VKP>`` and ``forest_image_kernel``) against
+"""The scoring kernels of ``ops/csrc/hip/tree_kernels.hip`` (``forest_predict_lds_kernel``, ``forest_predict_kernel``
+and ``forest_predict_multi_kernel<NS, KT, VKP>``) over the packed node image that ``forest_image_kernel`` builds,
+against
 
 * the numpy walk of tests/forest_predict_oracle.py, in its exact and its rounded regime, and
-* the kernels they replace (``TMOG_PREDICT_V1=1``, here reached by patching ``tree_engine.predict_v1``): in the
-  rounded regime, with random fp32 values and weights, every output must be bit-identical, because each output
-  element sees the same fp32 operations in the same order on both paths.
+* the same kernels over the direct node source (``TMOG_PREDICT_V1=1``, here reached by patching
+  ``tree_engine.predict_v1``): in the rounded regime, with random fp32 values and weights, every output must be
+  bit-identical, because each output element sees the same fp32 operations in the same order on both paths.
+
+Both paths run one kernel body, so the bit equality shows that the two node sources agree, not that two
+implementations do. The independent reference is the numpy walk: the exact regime by equality, the rounded regime
+within the walk's own bound, and each is asserted on both paths.
 
 One forest per (F, K) is built once and shared by the cases; the LDS kernels stage rows with 16-byte loads at F = 64,
 4-byte loads at F = 132 and the byte loop at F = 5; F = 513 takes the kernel that leaves rows in global memory."""
@@ -76,7 +81,7 @@ def _fresh(f):
 
 
 def _both(monkeypatch, call):
-    """``call()`` on the image path, then on the kernels it replaces."""
+    """``call()`` on the image path, then on the direct node source."""
     monkeypatch.setattr(te, "predict_v1", lambda: False)
     new = call()
     monkeypatch.setattr(te, "predict_v1", lambda: True)
@@ -236,7 +241,7 @@ def test_multi_all_rows_and_tree_counts(n, trees_i, monkeypatch):
 @pytest.mark.gpu
 def test_feature_index_past_16_bits_takes_the_direct_kernels():
     """A forest that splits on column 65540 does not fit the record: no image is built and the result is the
-    walk's (the kernels that read ``nodes`` directly)."""
+    walk's (the direct node source, which reads ``nodes``)."""
     rng = np.random.default_rng(77)
     F = 65600
     X = O.random_bins(rng, 65, F, B, B - 1)
@@ -251,7 +256,8 @@ def test_feature_index_past_16_bits_takes_the_direct_kernels():
 
 @pytest.mark.gpu
 def test_split_bin_past_8_bits_takes_the_direct_kernels():
-    """Split bin 300 (every bin goes left): outside the record, so the LDS and the variant kernel run directly."""
+    """Split bin 300 (every bin goes left): outside the record, so the LDS and the variant kernel run over the direct
+    node source."""
     f0, X, trees, w = _forest(64, 2, True)
     f = _fresh(f0)
     f.nodes = f0.nodes.copy()

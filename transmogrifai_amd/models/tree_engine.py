@@ -1011,8 +1011,9 @@ _PM_DEPTHS = 32                          # ... and its s_dmask: per-depth stop m
 
 
 def _pm_lds_bytes(F: int) -> int:
-    """LDS of one forest_predict_multi_kernel workgroup: 64 staged rows of F bins + 64 x 4 x 32 fp32
-    accumulators (tmog_hip_forest_predict_multi) + the kernel's static depth table."""
+    """The bytes ``tmog_hip_forest_predict_multi`` holds against the LDS limit: 64 staged rows of F bins + 64 x 4 x 32
+    fp32 sums + the kernel's static depth table. The kernel keeps its sums in registers and needs less; the figure
+    stays as the entry's refusal and as the width from which ``forest_predict_multi`` scores variant by variant."""
     return ((64 * F + 15) & ~15) + 4 * _PM_VK * 64 * 4 + 4 * (_PM_DEPTHS + 1)
 
 
@@ -1036,8 +1037,8 @@ def _lds_limit(dev) -> int:
 
 
 def predict_v1() -> bool:
-    """``TMOG_PREDICT_V1=1``: score with the kernels that read ``nodes`` / ``default_left`` / ``node_mask`` directly
-    instead of the packed node image (the A/B switch; read once per process by the native library)."""
+    """``TMOG_PREDICT_V1=1`` selects the direct node source: the scoring kernels read ``nodes`` / ``default_left`` /
+    ``node_mask`` instead of the packed node image (the A/B switch; read once per process by the native library)."""
     return bool(N.hip().tmog_hip_predict_v1())
 
 
@@ -1063,7 +1064,7 @@ def image_fits(forest: Forest) -> bool:
 
 def _scoring_image(forest: Forest, dev, mask_key=None, make_mask=None) -> Optional[torch.Tensor]:
     """The forest's node image on ``dev`` (int32 ``[n, 4]``), or None when the forest does not fit one (the caller
-    then scores with the direct kernels). Built by ``forest_image_kernel`` and kept on the forest object, per
+    then scores from the direct node source). Built by ``forest_image_kernel`` and kept on the forest object, per
     stream like the other device caches here: a fitted model scores every later batch from the same image. It is
     rebuilt when ``nodes`` or ``default_left`` (or, with variant masks, ``gain`` or the variants: ``mask_key``) is
     another object than the one it was built from; arrays edited in place are not noticed. ``make_mask()`` gives
@@ -1091,6 +1092,24 @@ def _scoring_image(forest: Forest, dev, mask_key=None, make_mask=None) -> Option
     return image
 
 
+def _batch_tables(Nrows: int, model_rows, model_trees):
+    """What a scoring call ships besides the forest: the trees reordered so that each model's are contiguous
+    (``order``, their offsets ``mto``) and each model's row count (``counts``, their offsets ``mro``)."""
+    order = [t for ts in model_trees for t in ts]
+    mto = np.zeros(len(model_trees) + 1, np.int64)
+    mto[1:] = np.cumsum([len(ts) for ts in model_trees])
+    counts = [Nrows if r is None else int(r.numel()) for r in model_rows]
+    mro = np.zeros(len(model_rows) + 1, np.int64)
+    mro[1:] = np.cumsum(counts)
+    return order, mto, counts, mro
+
+
+def _row_list(Nrows: int, model_rows, dev) -> torch.Tensor:
+    """The models' row ids back to back (int32), all rows for a model without a list."""
+    every = torch.arange(Nrows, device=dev, dtype=torch.int32) if any(r is None for r in model_rows) else None
+    return torch.cat([every if r is None else r.to(dev).to(torch.int32) for r in model_rows])
+
+
 def forest_predict_multi(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Optional[torch.Tensor]],
                          model_trees: Sequence[Sequence[int]],
                          model_variants: Sequence[Sequence[Tuple[int, float]]]) -> List[List[torch.Tensor]]:
@@ -1113,12 +1132,7 @@ def forest_predict_multi(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[
         return res
     Xb = Xb.contiguous()
     Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
-    order = [t for ts in model_trees for t in ts]
-    mto = np.zeros(len(model_trees) + 1, np.int64)
-    mto[1:] = np.cumsum([len(ts) for ts in model_trees])
-    counts = [Nrows if r is None else int(r.numel()) for r in model_rows]
-    mro = np.zeros(len(model_rows) + 1, np.int64)
-    mro[1:] = np.cumsum(counts)
+    order, mto, counts, mro = _batch_tables(Nrows, model_rows, model_trees)
     voff = np.zeros(len(model_variants) + 1, np.int32)
     voff[1:] = np.cumsum([len(v) for v in model_variants])
     vdep = np.asarray([d for vs in model_variants for d, _ in vs], np.int32)
@@ -1160,25 +1174,23 @@ def forest_predict_multi(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[
         ids += [pk.add(np.ascontiguousarray(forest.nodes)), pk.add(forest.default_left),
                 pk.add(make_mask().view(np.int32))]
     i_v = [pk.add(voff), pk.add(vdep), pk.add(vout), pk.add(mro), pk.add(mto)]
-    row_list = torch.cat([(torch.arange(Nrows, device=dev) if r is None else r.to(dev)).to(torch.int32)
-                          for r in model_rows])
+    row_list = _row_list(Nrows, model_rows, dev)
     dv = pk.ship()
     t_off, t_w, lv = (dv[i] for i in ids[:3])
     voff_t, vdep_t, vout_t, mro_t, mto_t = (dv[i] for i in i_v)
     out = torch.empty(max(pos, 1), dtype=torch.float32, device=dev)
+    # the two entries differ in how the nodes arrive and in what follows the class count
     if image is not None:
-        N.check(N.hip().tmog_hip_forest_predict_multi_image(
-            N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
-            N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(image), forest.missing_bin, N.ptr(lv), K, N.ptr(voff_t),
-            N.ptr(vdep_t), N.ptr(vout_t), max((len(v) for v in model_variants), default=0), N.ptr(out),
-            N.stream(dev)), "forest_predict_multi_image")
+        name, entry, node_args = "forest_predict_multi_image", N.hip().tmog_hip_forest_predict_multi_image, (N.ptr(image),)
+        tail = (N.ptr(voff_t), N.ptr(vdep_t), N.ptr(vout_t), max((len(v) for v in model_variants), default=0))
     else:
         nodes, dl, gn = (dv[i] for i in ids[3:])
-        N.check(N.hip().tmog_hip_forest_predict_multi(
-            N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
-            N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(nodes), N.ptr(dl), forest.missing_bin, N.ptr(lv), K,
-            N.ptr(gn), N.ptr(voff_t), N.ptr(vdep_t), N.ptr(vout_t), N.ptr(out), N.stream(dev)),
-            "forest_predict_multi")
+        name, entry, node_args = "forest_predict_multi", N.hip().tmog_hip_forest_predict_multi, (N.ptr(nodes), N.ptr(dl))
+        tail = (N.ptr(gn), N.ptr(voff_t), N.ptr(vdep_t), N.ptr(vout_t))
+    N.check(entry(
+        N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
+        N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), *node_args, forest.missing_bin, N.ptr(lv), K, *tail, N.ptr(out),
+        N.stream(dev)), name)
     res = []
     for m, vs in enumerate(model_variants):
         res.append([out[int(vout[int(voff[m]) + k]):int(vout[int(voff[m]) + k]) + counts[m] * K].view(counts[m], K)
@@ -1199,10 +1211,7 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
     Xb = Xb.contiguous()
     Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
     K = forest.K
-    # reorder trees so each model's trees are contiguous
-    order = [t for ts in model_trees for t in ts]
-    mto = np.zeros(len(model_trees) + 1, np.int64)
-    mto[1:] = np.cumsum([len(ts) for ts in model_trees])
+    order, mto, counts, mro = _batch_tables(Nrows, model_rows, model_trees)
     tw = np.ones(forest.n_trees, np.float32) if tree_weight is None else np.asarray(tree_weight, np.float32)
     image = None if dev.type != "cuda" or predict_v1() else _scoring_image(forest, dev)
     pk = _Pack(dev)
@@ -1210,16 +1219,9 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
            pk.add(np.ascontiguousarray(forest.value, np.float32))]
     if image is None:
         ids += [pk.add(np.ascontiguousarray(forest.nodes)), pk.add(forest.default_left)]
-    counts = [Nrows if r is None else int(r.numel()) for r in model_rows]
-    mro = np.zeros(len(model_rows) + 1, np.int64)
-    mro[1:] = np.cumsum(counts)
-    if all(r is None for r in model_rows):
-        row_list = None
-        if len(model_rows) > 1:
-            row_list = torch.cat([torch.arange(Nrows, device=dev, dtype=torch.int32)] * len(model_rows))
-    else:
-        row_list = torch.cat([(torch.arange(Nrows, device=dev) if r is None else r.to(dev)).to(torch.int32)
-                              for r in model_rows])
+    # a single all-rows model needs no list: the kernels compute the row from the block
+    single = len(model_rows) <= 1 and all(r is None for r in model_rows)
+    row_list = None if single else _row_list(Nrows, model_rows, dev)
     i_mro, i_mto = pk.add(mro), pk.add(mto)
     dv = pk.ship()
     t_off, t_w, lv = (dv[i] for i in ids[:3])
@@ -1227,21 +1229,19 @@ def forest_predict(forest: Forest, Xb: torch.Tensor, model_rows: Sequence[Option
     mro_t, mto_t = dv[i_mro], dv[i_mto]
     out = torch.zeros(int(mro[-1]), K, dtype=torch.float32, device=dev)
     if dev.type == "cuda":
+        if image is not None:
+            name, entry, node_args = "forest_predict_image", N.hip().tmog_hip_forest_predict_image, (N.ptr(image),)
+        else:
+            name, entry, node_args = "forest_predict", N.hip().tmog_hip_forest_predict, (N.ptr(nodes), N.ptr(dl))
         # the kernel accumulates up to 8 outputs per row in registers: wider K runs in class chunks
         for c0 in range(0, K, 8):
             kc = min(8, K - c0)
             lvc = lv if kc == K else lv[:, c0:c0 + kc].contiguous()
             oc = out if kc == K else torch.empty(int(mro[-1]), kc, dtype=torch.float32, device=dev)
-            if image is not None:
-                N.check(N.hip().tmog_hip_forest_predict_image(
-                    N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
-                    N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(image), forest.missing_bin, N.ptr(lvc), kc,
-                    N.ptr(oc), N.stream(dev)), "forest_predict_image")
-            else:
-                N.check(N.hip().tmog_hip_forest_predict(
-                    N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
-                    N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), N.ptr(nodes), N.ptr(dl), forest.missing_bin, N.ptr(lvc),
-                    kc, N.ptr(oc), N.stream(dev)), "forest_predict")
+            N.check(entry(
+                N.ptr(Xb), F, len(model_rows), N.ptr(mro_t), N.ptr(row_list), max(counts) if counts else 0,
+                N.ptr(mto_t), N.ptr(t_off), N.ptr(t_w), *node_args, forest.missing_bin, N.ptr(lvc), kc, N.ptr(oc),
+                N.stream(dev)), name)
             if kc != K:
                 out[:, c0:c0 + kc] = oc
     else:

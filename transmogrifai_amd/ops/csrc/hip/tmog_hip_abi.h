@@ -237,7 +237,8 @@ int tmog_hip_forest_predict(const uint8_t* Xb, int F, int n_models, const int64_
                             const uint8_t* default_left, int missing_bin, const float* leaf_value, int K, float* out,
                             hipStream_t stream);
 // The same scoring over a packed node image (16 bytes per node: feat | bin << 16 | default_left << 24, variant stop
-// mask, left, right) that tmog_hip_forest_image builds once per forest; tmog_hip_predict_v1 is TMOG_PREDICT_V1=1.
+// mask, left, right) that tmog_hip_forest_image builds once per forest; tmog_hip_predict_v1 is TMOG_PREDICT_V1=1,
+// which selects the direct node source (the two entries above) for every forest.
 int tmog_hip_predict_v1();
 int tmog_hip_forest_image(const int32_t* nodes, const uint8_t* default_left, const uint32_t* node_mask, int64_t n,
                           int32_t* image, hipStream_t stream);
