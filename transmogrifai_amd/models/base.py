@@ -140,6 +140,11 @@ class Learner:
         raise NotImplementedError(f"{self.name} has no exact SHAP attributions; RecordInsightsLOCO explains "
                                   "any model")
 
+    def shap_interaction_values(self, state, X: torch.Tensor, rows=None, context=None):
+        """Exact SHAP interaction values of the model's score (tree learners: TreeSHAP interactions)."""
+        raise NotImplementedError(f"{self.name} has no exact SHAP interaction values; RecordInsightsLOCO explains "
+                                  "any model")
+
     def loco_scores(self, state, X: torch.Tensor, groups=None, rows=None, context=None):
         """Exact leave-one-column-out scores without rescoring (tree learners: path perturbation):
         ``(base [n, C'], perturbed [n, U + G, C'], used)``, the score columns ``RecordInsightsLOCO`` ranks by."""

@@ -1531,6 +1531,64 @@ def forest_shap(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor] =
     return out, used64
 
 
+def forest_shap_interactions(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                             tree_weight: Optional[np.ndarray] = None, tree_out: Optional[np.ndarray] = None,
+                             n_out: Optional[int] = None,
+                             paths: Optional[ForestPaths] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """Exact SHAP interaction values of the score :func:`forest_shap` attributes (same arguments):
+    ``(Phi float64 [n, U + 1, U + 1, C], used_features int64 [U])``. ``Phi[:, i, j]`` with ``i != j < U`` is the
+    interaction of columns ``used_features[i]`` and ``used_features[j]`` (half the Shapley interaction index, so
+    the pair's whole effect is ``Phi[:, i, j] + Phi[:, j, i]``), ``Phi[:, i, i]`` the main effect, ``Phi[:, U, U]``
+    the bias and the rest of row and column ``U`` zero. ``Phi`` is exactly symmetric, ``Phi.sum(2)`` is
+    :func:`forest_shap`'s ``phi`` and ``Phi.sum((1, 2))`` the forest's prediction.
+
+    Device matrices run ``tmog_hip_forest_shap_interactions``; paths longer than 64 elements or a tile beyond the
+    LDS limit, and host matrices, run the host twin. Either fills the pair sums (each unordered pair once); the
+    transpose, the diagonal (``phi`` minus the row's pair sums) and the bias are added in torch on the matrix's
+    device. Memory: the result takes ``n * (U + 1)^2 * C * 8`` bytes and the pair sums as much again while it
+    is put together, so callers block their rows."""
+    fp = paths if paths is not None else forest_paths(forest, tree_weight, tree_out)
+    C = int(n_out) if n_out is not None else fp.n_out
+    if C < fp.n_out:
+        raise ValueError(f"n_out = {C} but the trees write {fp.n_out} columns")
+    dev = Xb.device
+    Xb = Xb.contiguous()
+    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
+    if fp.used.size and int(fp.used[-1]) >= F:
+        raise ValueError(f"the forest splits on column {int(fp.used[-1])}, the matrix has {F}")
+    U, P, KV = int(fp.used.size), int(fp.p_out.size), int(fp.p_val.shape[1])
+    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
+    n = Nrows if rows is None else int(row_list.numel())
+    used64 = fp.used.astype(np.int64)
+    tri = torch.empty(n, U, U, C, dtype=torch.float64, device=dev)
+    bo = fp.bin_off
+    if dev.type == "cuda":
+        d = fp.on(dev)
+        rc = N.hip().tmog_hip_forest_shap_interactions(
+            N.ptr(Xb), F, n, N.ptr(row_list), U, N.ptr(d[0]), P, N.ptr(d[1]), N.ptr(d[2]), N.ptr(d[3]), KV,
+            None, N.ptr(d[4]), N.ptr(d[5]), N.ptr(d[6]), bo.ctypes.data, fp.missing_bin, C, fp.scale,
+            N.ptr(tri), N.stream(dev))
+        if rc in (-2, -3):           # a path longer than 64 elements / one row x one column beyond the LDS limit
+            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
+            return forest_shap_interactions(forest, sub.cpu(), None, n_out=C, paths=fp)[0].to(dev), used64
+        N.check(rc, "forest_shap_interactions")
+    else:
+        N.check(N.host().tmog_forest_shap_interactions_cpu(
+            N.ptr(Xb), F, n, N.ptr(row_list), U, fp.used.ctypes.data, P, fp.p_off.ctypes.data,
+            fp.p_out.ctypes.data, fp.p_val.ctypes.data, KV, None, fp.e_feat.ctypes.data, fp.e_rng.ctypes.data,
+            fp.e_z.ctypes.data, bo.ctypes.data, fp.missing_bin, C, fp.scale, N.ptr(tri)),
+            "forest_shap_interactions_cpu")
+    phi = forest_shap(forest, Xb, row_list, n_out=C, paths=fp)[0]
+    Phi = torch.zeros(n, U + 1, U + 1, C, dtype=torch.float64, device=dev)
+    off = Phi[:, :U, :U]
+    torch.add(tri, tri.transpose(1, 2), out=off)
+    del tri
+    diag = phi[:, :U] - off.sum(2)
+    off.diagonal(dim1=1, dim2=2).copy_(diag.transpose(1, 2))
+    Phi[:, U, U] = phi[:, U]
+    return Phi, used64
+
+
 # ------------------------------------------------------------------------------------- path-perturbation LOCO
 @dataclass
 class ForestLoco:

@@ -386,12 +386,22 @@ class _ForestLearner(Learner):
         ``phi.sum(1)`` the raw class-vote sum of :meth:`raw_sum` (``C = K`` columns), for a regressor the
         prediction (a forest's sum divided by its tree count). Slot ``U`` is the bias."""
         forest, Xb = self._binned(state, X, context)
+        return TE.forest_shap(forest, Xb, rows, paths=self._shap_paths(state, forest))
+
+    def _shap_paths(self, state, forest):
         if "_shap_paths" not in state:
             w = None
             if not self.classification and self.is_forest:
                 w = np.full(forest.n_trees, 1.0 / max(1, int(state.get("num_trees", 1))))
             state["_shap_paths"] = TE.forest_paths(forest, w)
-        return TE.forest_shap(forest, Xb, rows, paths=state["_shap_paths"])
+        return state["_shap_paths"]
+
+    def shap_interaction_values(self, state, X, rows=None, context=None):
+        """Exact SHAP interaction values of the score :meth:`shap_values` attributes: ``(Phi float64
+        [n, U + 1, U + 1, C], used_features int64 [U])``, symmetric, with ``Phi.sum(2)`` the ``phi`` of
+        :meth:`shap_values`: main effects on the diagonal, the bias in cell ``[U, U]``."""
+        forest, Xb = self._binned(state, X, context)
+        return TE.forest_shap_interactions(forest, Xb, rows, paths=self._shap_paths(state, forest))
 
     def loco_scores(self, state, X, groups=None, rows=None, context=None):
         """Exact LOCO scores by tree-path perturbation (``TE.forest_loco``): ``(base [n, C'], perturbed
@@ -704,14 +714,32 @@ class _BoostLearner(Learner):
         forest, Xb = self._binned_for(state, X, context)
         multi = state.get("objective") in MULTI_OBJECTIVES
         K = int(state["n_classes"]) if multi else 1
-        if "_shap_paths" not in state:
-            tw = np.asarray(state["tree_weights"], np.float32).astype(np.float64)
-            state["_shap_paths"] = TE.forest_paths(forest, tw, np.arange(forest.n_trees) % K if multi else None)
-        phi, used = TE.forest_shap(forest, Xb, rows, n_out=K, paths=state["_shap_paths"])
+        phi, used = TE.forest_shap(forest, Xb, rows, n_out=K, paths=self._shap_paths(state, forest, K, multi))
         phi[:, -1, :] += float(state.get("base_margin", 0.0))
         if self.classification and not multi:
             phi = torch.cat([-phi, phi], 2)
         return phi, used
+
+    def _shap_paths(self, state, forest, K, multi):
+        if "_shap_paths" not in state:
+            tw = np.asarray(state["tree_weights"], np.float32).astype(np.float64)
+            state["_shap_paths"] = TE.forest_paths(forest, tw, np.arange(forest.n_trees) % K if multi else None)
+        return state["_shap_paths"]
+
+    def shap_interaction_values(self, state, X, rows=None, context=None):
+        """Exact SHAP interaction values of the margin: ``(Phi float64 [n, U + 1, U + 1, C], used_features
+        int64 [U])`` with the columns of :meth:`shap_values` (a binary classifier: ``(-Phi, +Phi)``), symmetric,
+        ``Phi.sum(2)`` the ``phi`` of :meth:`shap_values`; cell ``[U, U]`` is the bias (``base_margin``
+        included)."""
+        forest, Xb = self._binned_for(state, X, context)
+        multi = state.get("objective") in MULTI_OBJECTIVES
+        K = int(state["n_classes"]) if multi else 1
+        Phi, used = TE.forest_shap_interactions(forest, Xb, rows, n_out=K,
+                                                paths=self._shap_paths(state, forest, K, multi))
+        Phi[:, -1, -1, :] += float(state.get("base_margin", 0.0))
+        if self.classification and not multi:
+            Phi = torch.cat([-Phi, Phi], 3)
+        return Phi, used
 
     def loco_scores(self, state, X, groups=None, rows=None, context=None):
         """Exact LOCO scores by tree-path perturbation (``TE.forest_loco``): ``(base [n, C'], perturbed

@@ -254,6 +254,11 @@ int tmog_forest_shap_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row
                          int64_t P, const int64_t* p_off, const int32_t* p_out, const double* p_val, int KV,
                          const double* bias, const int32_t* e_feat, const int32_t* e_rng, const double* e_z,
                          const int64_t* bin_off, int missing_bin, int C, double scale, double* out);
+int tmog_forest_shap_interactions_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U,
+                                      const int32_t* used, int64_t P, const int64_t* p_off, const int32_t* p_out,
+                                      const double* p_val, int KV, const double* bias, const int32_t* e_feat,
+                                      const int32_t* e_rng, const double* e_z, const int64_t* bin_off,
+                                      int missing_bin, int C, double scale, double* tri);
 int tmog_find_splits_cpu(const double* sample, int64_t S, int F, int max_splits, double* out, int32_t* n_out);
 int64_t tmog_tree_finalize_cpu(int64_t n, int T, const int64_t* tree, const int64_t* feat_in, const int64_t* bin,
                                const uint8_t* dl, const double* gain, const double* tot, int S,

@@ -120,6 +120,11 @@ int tmog_hip_forest_shap(const uint8_t* Xb, int F, int64_t n, const int32_t* row
                          const double* bias, const int32_t* e_feat, const int32_t* e_rng, const double* e_z,
                          const int64_t* bin_off, int missing_bin, int C, double scale, double* out,
                          hipStream_t stream);
+int tmog_hip_forest_shap_interactions(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U,
+                                      const int32_t* used, int64_t P, const int64_t* p_off, const int32_t* p_out,
+                                      const double* p_val, int KV, const double* bias, const int32_t* e_feat,
+                                      const int32_t* e_rng, const double* e_z, const int64_t* bin_off,
+                                      int missing_bin, int C, double scale, double* tri, hipStream_t stream);
 
 // ---- hip/sparse_kernels.hip
 int tmog_hip_csr_spmm(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t N, const float* V, int C,

@@ -16,7 +16,9 @@ For tree models ``perturbation="paths"`` replaces the perturbed batches by exact
 answer only where it is tested on the record's own path, so only those path suffixes are walked again.
 
 Beyond the reference: ``RecordInsightsSHAP`` explains tree models with exact path-dependent TreeSHAP
-(``tree_engine.forest_shap``, HIP kernel ``ops/csrc/hip/shap_kernels.hip``) instead of perturbing columns.
+(``tree_engine.forest_shap``, HIP kernel ``ops/csrc/hip/shap_kernels.hip``) instead of perturbing columns, and
+``RecordInsightsSHAPInteractions`` splits those attributions into main effects and pair effects (exact SHAP
+interaction values, ``tree_engine.forest_shap_interactions``, the second kernel of the same file).
 """
 from __future__ import annotations
 
@@ -123,6 +125,45 @@ class InsightsColumn(ObjectColumn):
                for c in cols):
             return InsightsColumn(torch.cat([c.cols for c in cols]), torch.cat([c.diffs for c in cols]), cols[0].keys)
         return ObjectColumn(T.TextMap, np.concatenate([c.values for c in cols]))
+
+
+class PairInsightsColumn(InsightsColumn):
+    """``InsightsColumn`` whose insights are column pairs: column indices ``[n, K, 2]`` (smaller first, -1 = none),
+    pair effects ``[n, K, C]``; a key is the JSON array of the two columns' history objects."""
+
+    def _render(self, cols, diffs) -> Dict[str, str]:
+        return {"[" + self.keys[a] + "," + self.keys[b] + "]":
+                "[" + ",".join(f"[{j},{_jf(x)}]" for j, x in enumerate(dv)) + "]"
+                for (a, b), dv in zip(cols.tolist(), diffs.tolist()) if a >= 0}
+
+    def take(self, idx):
+        i = idx.to(self.cols.device, torch.long) if isinstance(idx, torch.Tensor) else \
+            torch.as_tensor(np.asarray(idx, np.int64), device=self.cols.device)
+        return PairInsightsColumn(self.cols.index_select(0, i), self.diffs.index_select(0, i), self.keys)
+
+    def to(self, device):
+        return PairInsightsColumn(self.cols.to(device), self.diffs.to(device), self.keys)
+
+    def null_mask(self):
+        return ~(self.cols[:, :, 0] >= 0).any(1).cpu()
+
+    @classmethod
+    def _concat(cls, cols):
+        if all(isinstance(c, PairInsightsColumn) and c.keys == cols[0].keys
+               and c.diffs.shape[1:] == cols[0].diffs.shape[1:] for c in cols):
+            return PairInsightsColumn(torch.cat([c.cols for c in cols]), torch.cat([c.diffs for c in cols]),
+                                      cols[0].keys)
+        return ObjectColumn(T.TextMap, np.concatenate([c.values for c in cols]))
+
+
+def parse_interaction_insights(insights: Dict[str, str]) -> Dict[Tuple[str, str], List[Tuple[int, float]]]:
+    """The inverse of ``RecordInsightsSHAPInteractions``' rendering: [history A, history B] JSON ->
+    ``{(column name A, column name B): [(score index, value)]}``."""
+    out = {}
+    for k, v in (insights or {}).items():
+        a, b = json.loads(k)
+        out[a.get("columnName"), b.get("columnName")] = [(int(i), float(x)) for i, x in json.loads(v)]
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- LOCO
@@ -408,30 +449,56 @@ class RecordInsightsSHAP(RecordInsightsLOCO):
         dev = X.device
         phi, used = self._shap(X)
         U, C = phi.shape[1] - 1, phi.shape[2]
-        if C == 1:
-            ex = torch.zeros(n, dtype=torch.long, device=dev)
-        elif C == 2:
-            ex = torch.ones(n, dtype=torch.long, device=dev)
-        else:
-            learner, state = self._learner_state()
-            ex = learner.predict(state, X)[0].reshape(-1).to(torch.long)
+        ex = self._score_column(X, C)
         cand, plain_col, gcols = self._shap_plan(hist, used, dev)
         m = int(plain_col.numel())
-        k = int(self.params["top_k"])
-        abs_mode = self.params["top_k_strategy"] == "abs"
-        kk = min(k, m)
-        K = min(k if abs_mode else 2 * k, 2 * kk)
+        K = self._top_width(m)
         if m == 0 or n == 0:
             return (torch.full((n, K), -1, dtype=torch.long, device=dev),
                     torch.zeros(n, K, C, dtype=torch.float64, device=dev))
         V = torch.zeros(n, m, C, dtype=torch.float64, device=dev)
         V.index_add_(1, cand, phi[:, :U])
+        Cc = self._reported_columns(X, plain_col, gcols)
+        sel, okK = self._top_candidates(V, ex)
+        colsK = torch.where(okK, Cc.gather(1, sel), torch.full_like(sel, -1))
+        diffsK = V.gather(1, sel[:, :, None].expand(n, K, C))
+        return colsK, diffsK
+
+    def _score_column(self, X: torch.Tensor, C: int) -> torch.Tensor:
+        """The score column candidates are ranked by, per record ``[n]`` (LOCO's choice: the only one, the
+        positive class, the predicted class)."""
+        n, dev = X.shape[0], X.device
+        if C == 1:
+            return torch.zeros(n, dtype=torch.long, device=dev)
+        if C == 2:
+            return torch.ones(n, dtype=torch.long, device=dev)
+        learner, state = self._learner_state()
+        return learner.predict(state, X)[0].reshape(-1).to(torch.long)
+
+    def _top_width(self, m: int) -> int:
+        """Insights per record when there are ``m`` candidates."""
+        k = int(self.params["top_k"])
+        return min(k if self.params["top_k_strategy"] == "abs" else 2 * k, 2 * min(k, m))
+
+    def _reported_columns(self, X: torch.Tensor, plain_col: torch.Tensor, gcols) -> torch.Tensor:
+        """The column every candidate is reported under, per record ``[n, m]``: a plain candidate's own column,
+        a group's first active column (its first split column when the record has none)."""
+        n, m, dev = X.shape[0], int(plain_col.numel()), X.device
         Cc = plain_col[None, :].expand(n, m).clone()
         n_plain = m - len(gcols)
         for g, (gct, first_used) in enumerate(gcols):
             active = X[:, gct] != 0
             Cc[:, n_plain + g] = torch.where(active.any(1), gct[active.to(torch.int8).argmax(1)],
                                              torch.full((n,), first_used, dtype=torch.long, device=dev))
+        return Cc
+
+    def _top_candidates(self, V: torch.Tensor, ex: torch.Tensor):
+        """The selection of :meth:`_shap_block` over the attributions ``V [n, m, C]`` by the score column ``ex``:
+        (selected candidate [n, K], whether the slot holds one [n, K])."""
+        n, m, C = V.shape
+        kk = min(int(self.params["top_k"]), m)
+        K = self._top_width(m)
+        abs_mode = self.params["top_k_strategy"] == "abs"
         val = V.gather(2, ex.view(n, 1, 1).expand(n, m, 1)).squeeze(2)
         valid = (V != 0).any(2)
         ninf = torch.full_like(val, -float("inf"))
@@ -442,11 +509,7 @@ class RecordInsightsSHAP(RecordInsightsLOCO):
         v = val.gather(1, idx)
         key = torch.where(ok, v.abs() if abs_mode else v, torch.full_like(v, -float("inf")))
         order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :K]
-        sel = idx.gather(1, order)
-        okK = ok.gather(1, order)
-        colsK = torch.where(okK, Cc.gather(1, sel), torch.full_like(sel, -1))
-        diffsK = V.gather(1, sel[:, :, None].expand(n, K, C))
-        return colsK, diffsK
+        return idx.gather(1, order), ok.gather(1, order)
 
     def bias(self, X: torch.Tensor) -> torch.Tensor:
         """The attribution's bias per score column, ``[C]``: what the insights of a record add up from."""
@@ -477,6 +540,100 @@ class RecordInsightsSHAP(RecordInsightsLOCO):
             raise ValueError("RecordInsightsSHAP has not seen vector metadata yet")
         cidx, diffs = self._shap_block(x, self.histories)
         return InsightsColumn(cidx, diffs, [_history_json(h) for h in self.histories]).row(0)
+
+
+@register_stage
+class RecordInsightsSHAPInteractions(RecordInsightsSHAP):
+    """Unary (OPVector -> TextMap) transformer wrapping a fitted tree model stage: exact SHAP interaction values
+    (``tree_engine.forest_shap_interactions``, the second kernel of ``ops/csrc/hip/shap_kernels.hip``). They split
+    the attribution of every candidate of ``RecordInsightsSHAP`` into a main effect and its pair effects with
+    every other candidate. The interaction matrix is folded onto the candidates on both axes, so a pair inside
+    one text / date group lands in that group's main effect. Per record the stage reports the top ``top_k``
+    candidate pairs by the pair effect ``Phi_ab + Phi_ba`` of the selecting score column (the selection of
+    ``RecordInsightsSHAP``, both strategies); the key of an insight is the JSON array of the two candidates'
+    column histories in column order. :meth:`main_effects` plus all pair effects plus :meth:`bias` add up to the
+    record's raw score."""
+    operation_name = "recordInsightsSHAPInteractions"
+    BLOCK_BYTES = 1 << 29            # one block's interaction matrix stays below about 512 MB
+
+    def _interactions(self, X: torch.Tensor, context=None):
+        learner, state = self._learner_state()
+        try:
+            return learner.shap_interaction_values(state, X, None, context)
+        except NotImplementedError as e:
+            raise ValueError(f"RecordInsightsSHAPInteractions needs a tree model: {e}") from e
+
+    def _folded(self, X: torch.Tensor, hist: List[dict]):
+        """The interaction matrix of one block folded onto the candidates: (V [n, m, m, C], plan)."""
+        Phi, used = self._interactions(X)
+        n, U, C = Phi.shape[0], Phi.shape[1] - 1, Phi.shape[3]
+        plan = self._shap_plan(hist, used, X.device)
+        cand, m = plan[0], int(plan[1].numel())
+        half = torch.zeros(n, m, U, C, dtype=torch.float64, device=X.device)
+        half.index_add_(1, cand, Phi[:, :U, :U])
+        del Phi
+        V = torch.zeros(n, m, m, C, dtype=torch.float64, device=X.device)
+        V.index_add_(2, cand, half)
+        return V, plan
+
+    def _pair_block(self, X: torch.Tensor, hist: List[dict]):
+        """Top-K pair effects of one block of records: (columns [n, K, 2] (smaller first, -1 = no insight),
+        pair effects [n, K, C])."""
+        n, dev = X.shape[0], X.device
+        V, (cand, plain_col, gcols) = self._folded(X, hist)
+        m, C = V.shape[1], V.shape[3]
+        ia, ib = torch.triu_indices(m, m, 1, device=dev)
+        K = self._top_width(int(ia.numel()))
+        if ia.numel() == 0 or n == 0:
+            return (torch.full((n, K, 2), -1, dtype=torch.long, device=dev),
+                    torch.zeros(n, K, C, dtype=torch.float64, device=dev))
+        Vp = V[:, ia, ib] + V[:, ib, ia]
+        del V
+        Cc = self._reported_columns(X, plain_col, gcols)
+        sel, okK = self._top_candidates(Vp, self._score_column(X, C))
+        ca, cb = Cc.gather(1, ia[sel]), Cc.gather(1, ib[sel])
+        pair = torch.stack([torch.minimum(ca, cb), torch.maximum(ca, cb)], 2)
+        colsK = torch.where(okK[:, :, None], pair, torch.full_like(pair, -1))
+        diffsK = Vp.gather(1, sel[:, :, None].expand(n, sel.shape[1], C))
+        return colsK, diffsK
+
+    def _block_rows(self, X: torch.Tensor) -> int:
+        if X.shape[0] == 0:
+            return 1
+        phi = self._shap(X[:1])[0]
+        return max(1, self.BLOCK_BYTES // (phi.shape[1] ** 2 * phi.shape[2] * 8))
+
+    def main_effects(self, X: torch.Tensor) -> torch.Tensor:
+        """The folded diagonal ``[n, m, C]``: every candidate's main effect (a group's includes the pairs
+        among its members), candidates in the order of ``RecordInsightsSHAP``'s plan."""
+        if self.histories is None:
+            raise ValueError("RecordInsightsSHAPInteractions has not seen vector metadata yet")
+        block = self._block_rows(X)
+        return torch.cat([self._folded(X[a:a + block], self.histories)[0].diagonal(dim1=1, dim2=2).transpose(1, 2)
+                          for a in range(0, max(X.shape[0], 1), block)])
+
+    def _run(self, X: torch.Tensor, hist: List[dict]):
+        block = self._block_rows(X)
+        parts = [self._pair_block(X[a:a + block], hist) for a in range(0, X.shape[0], block)] or \
+            [self._pair_block(X[:0], hist)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def transform_columns(self, *cols, ds=None):
+        vec: VectorColumn = cols[0]
+        if vec.metadata is not None:
+            self.histories = vec.metadata.column_history()
+        hist = self.histories
+        if hist is None:
+            raise ValueError("RecordInsightsSHAPInteractions needs the input vector metadata (column histories)")
+        cidx, diffs = self._run(vec.values, hist)
+        return PairInsightsColumn(cidx, diffs, [_history_json(h) for h in hist])
+
+    def transform_row(self, *values):
+        x = torch.as_tensor(np.asarray(values[0], np.float64))[None, :]
+        if self.histories is None:
+            raise ValueError("RecordInsightsSHAPInteractions has not seen vector metadata yet")
+        cidx, diffs = self._pair_block(x, self.histories)
+        return PairInsightsColumn(cidx, diffs, [_history_json(h) for h in self.histories]).row(0)
 
 
 # ---------------------------------------------------------------------------------------------- Corr
