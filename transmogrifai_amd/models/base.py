@@ -151,6 +151,14 @@ class Learner:
         raise NotImplementedError(f"{self.name} has no path-perturbation LOCO; RecordInsightsLOCO's rescore mode "
                                   "explains any model")
 
+    def partial_dependence(self, state, X: torch.Tensor, columns, rows=None, context=None, scale: str = "raw",
+                           ice: bool = False):
+        """Exact partial dependence of the model's score on each of ``columns`` over the model's own bin grid (tree
+        learners: step functions below the tree paths): ``(values [Q, NB, C'], valid [Q, NB], counts [Q, NB],
+        ice [n, Q, NB, C'] or None)``."""
+        raise NotImplementedError(f"{self.name} has no exact partial dependence; it is built on the bin grid of the "
+                                  "tree learners")
+
     def state_to_json(self, state: dict) -> dict:
         from ..utils.serde import encode
         return encode(state)

@@ -1716,3 +1716,81 @@ def forest_loco(forest: Forest, Xb: torch.Tensor, zero_bins, rows: Optional[torc
         lp.nodes.ctypes.data, lp.value.ctypes.data, KV, lp.tree_weight.ctypes.data, lp.tree_out.ctypes.data,
         lp.missing_bin, C, lp.scale, N.ptr(out)), "forest_loco_cpu")
     return out, used64
+
+
+# ------------------------------------------------------------------------------- partial dependence / ICE curves
+def forest_partial_dependence(forest: Forest, Xb: torch.Tensor, cols, n_grid: int,
+                              rows: Optional[torch.Tensor] = None, tree_weight: Optional[np.ndarray] = None,
+                              tree_out: Optional[np.ndarray] = None, n_out: Optional[int] = None,
+                              plan: Optional[ForestLoco] = None, ice: bool = False,
+                              _walks: Optional[np.ndarray] = None) -> torch.Tensor:
+    """Exact partial dependence of the forest's ``tree_weight``-weighted leaf-value sum on rows ``rows`` (None = all)
+    of the binned matrix, over the complete bin grid of the columns ``cols`` (Q distinct matrix columns; ones no
+    tree splits on are allowed, their curves are constant): float64 ``pd_sum [Q, NB, C]`` on the matrix's device,
+    ``pd_sum[q, b] = sum_r s(x_r with column cols[q] replaced by bin b)``, ``NB = n_grid`` the model's histogram
+    width (``BinSpec.B``, at most 256, the missing bin -- its last point -- included). With ``ice=True`` the
+    per-record curves ``ice [n, Q, NB, C]`` instead. Tree ``t``'s ``K`` leaf values go to columns
+    ``tree_out[t] .. tree_out[t] + K - 1`` of ``C = n_out``, as in :func:`forest_loco`, whose plan this reads
+    (``plan``: the prepared :func:`forest_loco_plan`, callers cache it).
+
+    The ICE result takes ``n * Q * NB * C * 8`` bytes (20 000 rows x 20 columns x 256 bins: 819 MB per output
+    column): callers that only reduce it should pass their rows in blocks.
+
+    Device matrices run ``tmog_hip_forest_pd``; host matrices, and a launch whose one row x one column is beyond
+    the LDS limit, run the host twin -- both sum the same int64 fixed-point integers, so they agree bit for bit.
+    ``_walks`` (host matrices only): an int64 ``[2]`` array that the host twin adds its counts of base walks and of
+    step-function walks to (``benchmarks/bench_partial_dependence.py``)."""
+    lp = plan if plan is not None else forest_loco_plan(forest, tree_weight, tree_out)
+    C = int(n_out) if n_out is not None else lp.n_out
+    if C < lp.n_out:
+        raise ValueError(f"n_out = {C} but the trees write {lp.n_out} columns")
+    dev = Xb.device
+    Xb = Xb.contiguous()
+    if Xb.dtype != torch.uint8 or Xb.dim() != 2:
+        raise ValueError("Xb must be a uint8 [N, F] matrix")
+    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
+    if lp.used.size and int(lp.used[-1]) >= F:
+        raise ValueError(f"the forest splits on column {int(lp.used[-1])}, the matrix has {F}")
+    NB = int(n_grid)
+    if not 1 <= NB <= 256:
+        raise ValueError(f"n_grid = {NB}: the grid is the model's histogram width, 1 .. 256")
+    if 0 <= lp.missing_bin < NB - 1:
+        raise ValueError(f"the missing bin {lp.missing_bin} must be the last point of the grid of {NB}")
+    cq = np.asarray(cols.cpu() if isinstance(cols, torch.Tensor) else cols, np.int64).reshape(-1)
+    Q = int(cq.size)
+    if Q and (int(cq.min()) < 0 or int(cq.max()) >= F):
+        raise ValueError("cols names a column outside the matrix")
+    if np.unique(cq).size != Q:
+        raise ValueError("cols must be distinct")
+    slot_of = np.full(F, -1, np.int32)
+    slot_of[cq] = np.arange(Q, dtype=np.int32)
+    slot_of_used = np.ascontiguousarray(slot_of[lp.used], np.int32)
+    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
+    n = Nrows if rows is None else int(row_list.numel())
+    if row_list is not None and n and not (0 <= int(row_list.min()) and int(row_list.max()) < Nrows):
+        raise ValueError("rows names a row outside the matrix")
+    U, T, KV = int(lp.used.size), int(lp.tree_weight.size), int(lp.value.shape[1])
+    # the sum of n rows at a scale smaller by 2^ceil(log2 n): the same bound as one row's curve
+    scale = lp.scale if ice else lp.scale / 2.0 ** max(0, (n - 1).bit_length())
+    shape = (n, Q, NB, C) if ice else (Q, NB, C)
+    if dev.type == "cuda":
+        d = lp.on(dev)
+        slot_d = _const_tensor(slot_of_used, dev)
+        out = torch.empty(shape, dtype=torch.float64, device=dev) if ice else \
+            torch.zeros(shape, dtype=torch.int64, device=dev)
+        rc = N.hip().tmog_hip_forest_pd(
+            N.ptr(Xb), F, n, N.ptr(row_list), U, N.ptr(d[0]), N.ptr(slot_d), Q, NB, T, N.ptr(d[1]), N.ptr(d[2]),
+            int(lp.nodes.shape[0]), N.ptr(d[3]), KV, N.ptr(d[4]), N.ptr(d[5]), lp.missing_bin, C, scale,
+            0 if ice else 1, N.ptr(out), N.stream(dev))
+        if rc == -3:                 # one row x one column beyond the LDS limit
+            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
+            return forest_partial_dependence(forest, sub.cpu(), cq, NB, None, n_out=C, plan=lp, ice=ice).to(dev)
+        N.check(rc, "forest_pd")
+        return out if ice else out.to(torch.float64) * (1.0 / scale)
+    out = torch.empty(shape, dtype=torch.float64)
+    N.check(N.host().tmog_forest_pd_cpu(
+        N.ptr(Xb), F, n, N.ptr(row_list), U, lp.used.ctypes.data, slot_of_used.ctypes.data, Q, NB, T,
+        lp.tree_off.ctypes.data, lp.nodes.ctypes.data, lp.value.ctypes.data, KV, lp.tree_weight.ctypes.data,
+        lp.tree_out.ctypes.data, lp.missing_bin, C, scale, 0 if ice else 1, N.ptr(out),
+        None if _walks is None else _walks.ctypes.data), "forest_pd_cpu")
+    return out

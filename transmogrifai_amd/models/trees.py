@@ -113,6 +113,13 @@ def _zero_bins(X: torch.Tensor, spec: BinSpec) -> torch.Tensor:
     return quantize(torch.zeros(1, int(X.shape[1]), dtype=X.dtype, device=X.device), spec)[0]
 
 
+def _score_columns(outputs) -> torch.Tensor:
+    """The score columns of a learner's ``(prediction, raw, probability)``: the probabilities if it has them, else
+    the prediction as one column (fp64)."""
+    pred, _, prob = outputs
+    return (prob if prob.shape[1] > 0 else pred.reshape(-1, 1)).to(torch.float64)
+
+
 def _loco_outputs(outputs, out: torch.Tensor, base_margin: float):
     """``TE.forest_loco``'s sums ``[n, U + G + 1, C]`` through a learner's ``outputs(sums [k, C]) -> (prediction,
     raw, probability)``: ``(base [n, C'], perturbed [n, U + G, C'])``, base + delta formed in fp64; the score columns
@@ -127,6 +134,55 @@ def _loco_outputs(outputs, out: torch.Tensor, base_margin: float):
     base = scores(base_sum)
     pert = scores((base_sum[:, None, :] + out[:, :-1, :]).reshape(n * m, C))
     return base, pert.reshape(n, m, int(base.shape[1]))
+
+
+PD_ICE_BLOCK_BYTES = 256 << 20      # the ICE curves of one row block of the response scale
+
+
+def _partial_dependence(forest, spec: BinSpec, Xb: torch.Tensor, plan, columns, rows, n_out: int, raw_of, scores,
+                        scale: str, ice: bool):
+    """``partial_dependence`` of the tree learners over ``TE.forest_partial_dependence``. ``raw_of(sums [..., C])``
+    maps the additive sums to the columns ``shap_values`` attributes (linear: applied to the mean),
+    ``scores(sums [k, C]) -> [k, C']`` to the probabilities / the prediction (applied per curve point, in row
+    blocks of ICE curves). ``(values [Q, NB, C'], valid [Q, NB], counts [Q, NB], ice or None)``."""
+    if scale not in ("raw", "response"):
+        raise ValueError(f"scale must be 'raw' or 'response', got {scale!r}")
+    dev = Xb.device
+    cols = np.asarray(columns.cpu() if isinstance(columns, torch.Tensor) else columns, np.int64).reshape(-1)
+    Q, NB, F = int(cols.size), int(spec.B), int(Xb.shape[1])
+    if Q and (int(cols.min()) < 0 or int(cols.max()) >= F):
+        raise ValueError("columns names a column outside the feature vector")
+    rows = None if rows is None else torch.as_tensor(rows).to(dev).to(torch.long).reshape(-1)
+    n = int(Xb.shape[0]) if rows is None else int(rows.numel())
+    if n == 0:
+        raise ValueError("partial dependence needs at least one row")
+    cd = torch.as_tensor(cols, device=dev)
+    sel = (Xb if rows is None else Xb.index_select(0, rows)).index_select(1, cd).to(torch.long)
+    counts = torch.bincount((sel.clamp_max(NB - 1) + torch.arange(Q, device=dev) * NB).reshape(-1),
+                            minlength=Q * NB).reshape(Q, NB)
+    b = torch.arange(NB, device=dev)
+    valid = b[None, :] < torch.as_tensor(spec.n_bins[cols].astype(np.int64), device=dev)[:, None]
+    if spec.missing_bin >= 0:
+        valid = valid | (b[None, :] == int(spec.missing_bin))
+    curves = None
+    if scale == "raw":
+        values = raw_of(TE.forest_partial_dependence(forest, Xb, cols, NB, rows, n_out=n_out, plan=plan) / n)
+    if scale == "response" or ice:
+        block = max(1, PD_ICE_BLOCK_BYTES // max(1, Q * NB * n_out * 8))
+        total, kept = None, []
+        for a in range(0, n, block):
+            r = torch.arange(a, min(n, a + block), device=dev) if rows is None else rows[a:a + block]
+            c = TE.forest_partial_dependence(forest, Xb, cols, NB, r, n_out=n_out, plan=plan, ice=True)
+            c = raw_of(c) if scale == "raw" else scores(c.reshape(-1, n_out)).reshape(c.shape[0], Q, NB, -1)
+            if scale == "response":
+                total = c.sum(0) if total is None else total + c.sum(0)
+            if ice:
+                kept.append(c)
+        if scale == "response":
+            values = total / n
+        if ice:
+            curves = torch.cat(kept, 0)
+    return values, valid, counts, curves
 
 
 def _subset_size(strategy, F: int, classification: bool, num_trees: int) -> int:
@@ -415,6 +471,22 @@ class _ForestLearner(Learner):
                                    plan=state["_loco_plan"])
         base, pert = _loco_outputs(lambda raw: self._outputs(state, raw), out, 0.0)
         return base, pert, used
+
+    def partial_dependence(self, state, X, columns, rows=None, context=None, scale="raw", ice=False):
+        """Exact partial dependence of the score on each of ``columns`` (columns of the feature vector) over the
+        model's complete bin grid (``TE.forest_partial_dependence``): ``(values float64 [Q, NB, C'], valid bool
+        [Q, NB], counts int64 [Q, NB], ice [n, Q, NB, C'] or None)`` for rows ``rows`` (None: all). ``scale="raw"``:
+        the mean of what :meth:`shap_values` attributes (the class-vote sums, a regressor's prediction), summed in
+        the kernel; ``scale="response"``: the mean of the probabilities (a regressor: the prediction), every ICE
+        curve pushed through ``_outputs`` in row blocks. ``valid`` marks the bins the column has (and the missing
+        bin), ``counts`` how many of the rows sit in each bin; ``ice=True`` also returns the per-record curves."""
+        forest, Xb = self._binned(state, X, context)
+        if "_loco_plan" not in state:
+            state["_loco_plan"] = TE.forest_loco_plan(forest)
+        div = max(1, int(state.get("num_trees", 1))) if (not self.classification and self.is_forest) else 1
+        return _partial_dependence(forest, self._forest(state)[1], Xb, state["_loco_plan"], columns, rows,
+                                   state["_loco_plan"].n_out, lambda s: s / div if div != 1 else s,
+                                   lambda s: _score_columns(self._outputs(state, s)), scale, ice)
 
     def predict_batch(self, states, X, rows, context=None):
         if not states:
@@ -758,6 +830,32 @@ class _BoostLearner(Learner):
         base, pert = _loco_outputs(lambda m: self._outputs(state, m if multi else m[:, 0]), out,
                                    float(state.get("base_margin", 0.0)))
         return base, pert, used
+
+    def partial_dependence(self, state, X, columns, rows=None, context=None, scale="raw", ice=False):
+        """Exact partial dependence of the score on each of ``columns`` (columns of the feature vector) over the
+        model's complete bin grid (``TE.forest_partial_dependence``): ``(values float64 [Q, NB, C'], valid bool
+        [Q, NB], counts int64 [Q, NB], ice [n, Q, NB, C'] or None)`` for rows ``rows`` (None: all). ``scale="raw"``:
+        the mean of what :meth:`shap_values` attributes (the margin with ``base_margin``, ``(-m, m)`` for a binary
+        classifier, the K margins of a multiclass model), summed in the kernel; ``scale="response"``: the mean of
+        the probabilities (a regressor: the prediction), every ICE curve pushed through ``_outputs`` in row blocks.
+        ``valid`` marks the bins the column has (and the missing bin), ``counts`` how many of the rows sit in each
+        bin; ``ice=True`` also returns the per-record curves."""
+        forest, Xb = self._binned_for(state, X, context)
+        multi = state.get("objective") in MULTI_OBJECTIVES
+        K = int(state["n_classes"]) if multi else 1
+        if "_loco_plan" not in state:
+            state["_loco_plan"] = TE.forest_loco_plan(forest, np.asarray(state["tree_weights"], np.float32),
+                                                      np.arange(forest.n_trees) % K if multi else None)
+        bm = float(state.get("base_margin", 0.0))
+        binary = self.classification and not multi
+
+        def raw_of(s):
+            m = s + bm
+            return torch.cat([-m, m], -1) if binary else m
+
+        return _partial_dependence(forest, self._forest(state)[1], Xb, state["_loco_plan"], columns, rows, K, raw_of,
+                                   lambda s: _score_columns(self._outputs(state, (s + bm) if multi else s[:, 0] + bm)),
+                                   scale, ice)
 
     def predict_batch(self, states, X, rows, context=None):
         return [self._outputs(s, self.margin(s, X, r, context)) for s, r in zip(states, rows)]

@@ -196,6 +196,23 @@ int tmog_forest_loco_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row
                          const float* value, int KV, const float* tree_weight, const int32_t* tree_out,
                          int missing_bin, int C, double scale, double* out);
 
+// ---- host/pd_cpu.cpp
+// Exact partial dependence / ICE curves over the complete bin grid: for rows row_list[0 .. n) (null: rows 0 .. n-1)
+// of Xb [.][F] and the Q requested columns, ice[i][q][b][C] = the forest's weighted leaf-value sum of row i with
+// the q-th requested column replaced by bin b, b in [0, NB). nodes, used, value, tree_weight, tree_out, C are those
+// of tmog_forest_loco_cpu; slot_of_used[u] = q of column used[u], or -1 when it is not requested (a requested
+// column no tree splits on has no entry: its curve is the unperturbed sum). A missing bin inside the grid must be
+// its last point, NB - 1; it follows the nodes' default directions. mode 0: out is ice, fp64 [n][Q][NB][C];
+// mode != 0: out is the sum over the rows, fp64 [Q][NB][C]. Every contribution is rounded to the int64 fixed
+// point of the power of two `scale` and summed as integers (hip/pd_kernels.hip has the rule and the bound; the
+// sum takes a scale smaller by 2^ceil(log2 n)). walks (may be null): [0] += base walks, [1] += the walks of the
+// step functions below them. Returns -1 for a grid the rule above excludes.
+int tmog_forest_pd_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
+                       const int32_t* slot_of_used, int Q, int NB, int64_t T, const int64_t* tree_off,
+                       const int32_t* nodes, const float* value, int KV, const float* tree_weight,
+                       const int32_t* tree_out, int missing_bin, int C, double scale, int mode, double* out,
+                       int64_t* walks);
+
 // ---- host/streaming_histogram.cpp
 void* tmog_shist_new(int max_bins, int max_spool, int64_t round_to);
 void tmog_shist_free(void* h);

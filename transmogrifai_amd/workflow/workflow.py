@@ -557,6 +557,14 @@ class OpWorkflowModel(OpWorkflowCore):
         feat = feature or next((f for f in self.result_features if f.wtype.__name__ == "Prediction"), None)
         return extract_model_insights(self, feat)
 
+    def partial_dependence(self, data=None, features=None, top_k: int = 10, scale: str = "response",
+                           sample: Optional[int] = 10_000, seed: int = 0, ice: bool = False,
+                           feature: Optional[FeatureLike] = None):
+        """Exact partial dependence / ICE curves of the selected tree model over its bin grid
+        (``insights.partial_dependence.partial_dependence`` has the arguments)."""
+        from ..insights.partial_dependence import partial_dependence
+        return partial_dependence(self, data, features, top_k, scale, sample, seed, ice, feature)
+
     def summary_json(self) -> Dict:
         from ..selector.model_selector import ModelSelector
         out = {}
