@@ -1370,9 +1370,71 @@ def forest_staged_eval(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Te
     return staged_eval_finish(raw, int(margins.shape[0]), metric), margins
 
 
+# ------------------------------------------------------------- forest explanations: what the four engines share
+def _pow2_scale(S: float, bits: int) -> float:
+    """The power of two with ``S * scale < 2^bits`` (1.0 for a forest without magnitude): the kernels' fixed point."""
+    if not (S > 0 and math.isfinite(S)):
+        return 1.0
+    return 2.0 ** max(-1000, min(1000, bits - math.frexp(S)[1]))
+
+
+def _split_columns(forest: Forest) -> Tuple[np.ndarray, np.ndarray]:
+    """``(internal, used)``: which nodes split, and the distinct columns they split on, sorted (int32)."""
+    internal = forest.nodes[:, 2] >= 0
+    return internal, np.unique(forest.nodes[internal, 0]).astype(np.int32)
+
+
+def _columns_needed(forest: Forest, tout: np.ndarray) -> int:
+    """The output columns the trees write: tree ``t`` fills ``tout[t] .. tout[t] + K - 1``."""
+    return (int(tout.max()) if forest.n_trees else 0) + forest.K
+
+
+def _magnitude_bound(forest: Forest, tw: np.ndarray, value: np.ndarray) -> float:
+    """``S = sum_t |w_t| max_node |value_t|`` in the precision of the caller's weights and values."""
+    S = 0.0
+    for t in range(forest.n_trees):
+        a, b = int(forest.tree_off[t]), int(forest.tree_off[t + 1])
+        if b > a and value[a:b].size:
+            S += abs(float(tw[t])) * float(np.abs(value[a:b]).max())
+    return float(S)
+
+
+class _Resident:
+    """The arrays ``_shipped`` names, resident on a device (shipped once per device)."""
+    _shipped: Tuple[str, ...] = ()
+
+    def on(self, dev):
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(getattr(self, a))).to(dev)
+                                   for a in self._shipped)
+        return self._dev[key]
+
+
+def _explain_rows(plan, Xb: torch.Tensor, rows: Optional[torch.Tensor], n_out: Optional[int]):
+    """What every explanation engine derives first: ``(Xb contiguous, Nrows, F, C output columns, row_list int32 on
+    the matrix's device or None, n rows served, the plan's used columns as int64)``."""
+    C = int(n_out) if n_out is not None else plan.n_out
+    if C < plan.n_out:
+        raise ValueError(f"n_out = {C} but the trees write {plan.n_out} columns")
+    Xb = Xb.contiguous()
+    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
+    if plan.used.size and int(plan.used[-1]) >= F:
+        raise ValueError(f"the forest splits on column {int(plan.used[-1])}, the matrix has {F}")
+    row_list = None if rows is None else rows.to(Xb.device).to(torch.int32).contiguous()
+    n = Nrows if rows is None else int(row_list.numel())
+    return Xb, Nrows, F, C, row_list, n, plan.used.astype(np.int64)
+
+
+def _on_host_twin(Xb: torch.Tensor, row_list: Optional[torch.Tensor], run) -> torch.Tensor:
+    """The answer for a launch the device entry refused: ``run`` on the CPU copy of the rows, moved back."""
+    sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
+    return run(sub.cpu()).to(Xb.device)
+
+
 # ------------------------------------------------------------------------------------------ TreeSHAP
 @dataclass
-class ForestPaths:
+class ForestPaths(_Resident):
     """One merged path per leaf (:func:`forest_paths`), ordered by length bin (m <= 16, <= 32, <= 64, longer),
     then by tree. Element arrays are indexed ``p_off[p] .. p_off[p + 1]``."""
     used: np.ndarray                # int32 [U]   distinct split features, sorted
@@ -1388,21 +1450,12 @@ class ForestPaths:
     S: float                        # sum_t |w_t| max_node |value_t|: the attribution's magnitude bound
     missing_bin: int = -1
     _dev: dict = field(default_factory=dict, repr=False)
+    _shipped = ("used", "p_off", "p_out", "p_val", "e_feat", "e_rng", "e_z")
 
     @property
     def scale(self) -> float:
-        """The power of two with ``S * scale < 2^62`` (fixed-point accumulation of the HIP kernel)."""
-        if not (self.S > 0 and math.isfinite(self.S)):
-            return 1.0
-        return 2.0 ** max(-1000, min(1000, 62 - math.frexp(self.S)[1]))
-
-    def on(self, dev):
-        """The arrays the kernel reads, resident on ``dev`` (shipped once)."""
-        key = str(dev)
-        if key not in self._dev:
-            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (
-                self.used, self.p_off, self.p_out, self.p_val, self.e_feat, self.e_rng, self.e_z))
-        return self._dev[key]
+        """``S * scale < 2^62``: a row's partial sums stay below ``2 S`` (``ops/csrc/hip/shap_kernels.hip``)."""
+        return _pow2_scale(self.S, 62)
 
 
 def forest_paths(forest: Forest, tree_weight: Optional[np.ndarray] = None,
@@ -1418,18 +1471,15 @@ def forest_paths(forest: Forest, tree_weight: Optional[np.ndarray] = None,
     tw = np.ones(T, np.float64) if tree_weight is None else np.asarray(tree_weight, np.float64)
     tout = np.zeros(T, np.int32) if tree_out is None else np.asarray(tree_out, np.int32)
     nd = forest.nodes
-    internal = nd[:, 2] >= 0
-    used = np.unique(nd[internal, 0]).astype(np.int32)
+    used = _split_columns(forest)[1]
     cover = forest.cover.astype(np.float64)
     value = forest.value.astype(np.float64)
     dl = forest.default_left
     paths = []                       # (m, tree, feats, los, his, miss, zs, leaf)
-    S = 0.0
     for t in range(T):
         a, b = int(forest.tree_off[t]), int(forest.tree_off[t + 1])
         if b <= a:
             continue
-        S += abs(tw[t]) * float(np.abs(value[a:b]).max()) if value[a:b].size else 0.0
         stack = [(a, ())]            # (node, elements: tuple of (feat, lo, hi, miss_ok, z) in order of first use)
         while stack:
             k, els = stack.pop()
@@ -1477,12 +1527,12 @@ def forest_paths(forest: Forest, tree_weight: Optional[np.ndarray] = None,
     e_feat = np.searchsorted(used, e_feat).astype(np.int32)
     sb = bins[order]
     bin_off = np.asarray([0, np.sum(sb <= 0), np.sum(sb <= 1), np.sum(sb <= 2)], np.int64)
-    n_out = (int(tout.max()) if T else 0) + KV
+    n_out = _columns_needed(forest, tout)
     bias = np.zeros(n_out, np.float64)
     for c in range(KV):
         np.add.at(bias, p_out + c, p_val[:, c] * p_zprod)
-    return ForestPaths(used, p_off, p_out, p_val, bias, e_feat, e_rng, e_z, bin_off, n_out, float(S),
-                       int(forest.missing_bin))
+    return ForestPaths(used, p_off, p_out, p_val, bias, e_feat, e_rng, e_z, bin_off, n_out,
+                       _magnitude_bound(forest, tw, value), int(forest.missing_bin))
 
 
 def forest_shap(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor] = None,
@@ -1496,18 +1546,9 @@ def forest_shap(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor] =
     than 64 elements or a tile beyond the LDS limit, and host matrices, run the host twin. ``paths``: the
     prepared :func:`forest_paths` of the same forest / weights / columns (callers cache them)."""
     fp = paths if paths is not None else forest_paths(forest, tree_weight, tree_out)
-    C = int(n_out) if n_out is not None else fp.n_out
-    if C < fp.n_out:
-        raise ValueError(f"n_out = {C} but the trees write {fp.n_out} columns")
     dev = Xb.device
-    Xb = Xb.contiguous()
-    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
-    if fp.used.size and int(fp.used[-1]) >= F:
-        raise ValueError(f"the forest splits on column {int(fp.used[-1])}, the matrix has {F}")
+    Xb, _, F, C, row_list, n, used64 = _explain_rows(fp, Xb, rows, n_out)
     U, P, KV = int(fp.used.size), int(fp.p_out.size), int(fp.p_val.shape[1])
-    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
-    n = Nrows if rows is None else int(row_list.numel())
-    used64 = fp.used.astype(np.int64)
     out = torch.empty(n, U + 1, C, dtype=torch.float64, device=dev)
     bo = fp.bin_off
     bias = np.zeros(C, np.float64)
@@ -1520,8 +1561,7 @@ def forest_shap(forest: Forest, Xb: torch.Tensor, rows: Optional[torch.Tensor] =
             N.ptr(bias_d), N.ptr(d[4]), N.ptr(d[5]), N.ptr(d[6]), bo.ctypes.data, fp.missing_bin, C, fp.scale,
             N.ptr(out), N.stream(dev))
         if rc in (-2, -3):           # a path longer than 64 elements / one row's tile beyond the LDS limit
-            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
-            return forest_shap(forest, sub.cpu(), None, n_out=C, paths=fp)[0].to(dev), used64
+            return _on_host_twin(Xb, row_list, lambda sub: forest_shap(forest, sub, None, n_out=C, paths=fp)[0]), used64
         N.check(rc, "forest_shap")
         return out, used64
     N.check(N.host().tmog_forest_shap_cpu(
@@ -1548,18 +1588,9 @@ def forest_shap_interactions(forest: Forest, Xb: torch.Tensor, rows: Optional[to
     device. Memory: the result takes ``n * (U + 1)^2 * C * 8`` bytes and the pair sums as much again while it
     is put together, so callers block their rows."""
     fp = paths if paths is not None else forest_paths(forest, tree_weight, tree_out)
-    C = int(n_out) if n_out is not None else fp.n_out
-    if C < fp.n_out:
-        raise ValueError(f"n_out = {C} but the trees write {fp.n_out} columns")
     dev = Xb.device
-    Xb = Xb.contiguous()
-    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
-    if fp.used.size and int(fp.used[-1]) >= F:
-        raise ValueError(f"the forest splits on column {int(fp.used[-1])}, the matrix has {F}")
+    Xb, _, F, C, row_list, n, used64 = _explain_rows(fp, Xb, rows, n_out)
     U, P, KV = int(fp.used.size), int(fp.p_out.size), int(fp.p_val.shape[1])
-    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
-    n = Nrows if rows is None else int(row_list.numel())
-    used64 = fp.used.astype(np.int64)
     tri = torch.empty(n, U, U, C, dtype=torch.float64, device=dev)
     bo = fp.bin_off
     if dev.type == "cuda":
@@ -1569,8 +1600,8 @@ def forest_shap_interactions(forest: Forest, Xb: torch.Tensor, rows: Optional[to
             None, N.ptr(d[4]), N.ptr(d[5]), N.ptr(d[6]), bo.ctypes.data, fp.missing_bin, C, fp.scale,
             N.ptr(tri), N.stream(dev))
         if rc in (-2, -3):           # a path longer than 64 elements / one row x one column beyond the LDS limit
-            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
-            return forest_shap_interactions(forest, sub.cpu(), None, n_out=C, paths=fp)[0].to(dev), used64
+            return _on_host_twin(
+                Xb, row_list, lambda sub: forest_shap_interactions(forest, sub, None, n_out=C, paths=fp)[0]), used64
         N.check(rc, "forest_shap_interactions")
     else:
         N.check(N.host().tmog_forest_shap_interactions_cpu(
@@ -1591,7 +1622,7 @@ def forest_shap_interactions(forest: Forest, Xb: torch.Tensor, rows: Optional[to
 
 # ------------------------------------------------------------------------------------- path-perturbation LOCO
 @dataclass
-class ForestLoco:
+class ForestLoco(_Resident):
     """What :func:`forest_loco` reads of one forest / weights / output columns (:func:`forest_loco_plan`)."""
     used: np.ndarray                # int32 [U]   distinct split columns, sorted
     nodes: np.ndarray               # int32 [n, 4] (slot u, bin | default_left << 16, left, right), left < 0 => leaf
@@ -1603,22 +1634,13 @@ class ForestLoco:
     S: float                        # sum_t |w_t| max_node |value_t|: the magnitude bound of the base sum
     missing_bin: int = -1
     _dev: dict = field(default_factory=dict, repr=False)
+    _shipped = ("used", "tree_off", "nodes", "value", "tree_weight", "tree_out")
 
     @property
     def scale(self) -> float:
-        """The power of two with ``S * scale < 2^61``: a delta slot's partial sums stay within ``2 S``
-        (``ops/csrc/hip/loco_kernels.hip`` has the bound), so the int64 fixed-point sums cannot overflow."""
-        if not (self.S > 0 and math.isfinite(self.S)):
-            return 1.0
-        return 2.0 ** max(-1000, min(1000, 61 - math.frexp(self.S)[1]))
-
-    def on(self, dev):
-        """The arrays the kernel reads, resident on ``dev`` (shipped once)."""
-        key = str(dev)
-        if key not in self._dev:
-            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (
-                self.used, self.tree_off, self.nodes, self.value, self.tree_weight, self.tree_out))
-        return self._dev[key]
+        """``S * scale < 2^61``: a delta slot's partial sums stay within ``2 S`` (``ops/csrc/hip/loco_kernels.hip``
+        has the bound), so the int64 fixed-point sums cannot overflow."""
+        return _pow2_scale(self.S, 61)
 
 
 def forest_loco_plan(forest: Forest, tree_weight: Optional[np.ndarray] = None,
@@ -1634,8 +1656,7 @@ def forest_loco_plan(forest: Forest, tree_weight: Optional[np.ndarray] = None,
     if T and int(tout.min()) < 0:
         raise ValueError("tree_out must not be negative")
     nd = forest.nodes
-    internal = nd[:, 2] >= 0
-    used = np.unique(nd[internal, 0]).astype(np.int32)
+    internal, used = _split_columns(forest)
     if internal.any() and (int(nd[internal, 1].min()) < 0 or int(nd[internal, 1].max()) > 0xFFFF):
         raise ValueError("split bins must fit 16 bits")
     nodes = np.zeros((len(nd), 4), np.int32)
@@ -1644,14 +1665,8 @@ def forest_loco_plan(forest: Forest, tree_weight: Optional[np.ndarray] = None,
     nodes[:, 2] = np.where(internal, nd[:, 2], -1)
     nodes[:, 3] = np.where(internal, nd[:, 3], -1)
     value = np.ascontiguousarray(forest.value, np.float32).reshape(len(nd), -1)
-    S = 0.0
-    for t in range(T):
-        a, b = int(forest.tree_off[t]), int(forest.tree_off[t + 1])
-        if b > a and value[a:b].size:
-            S += abs(float(tw[t])) * float(np.abs(value[a:b]).max())
-    n_out = (int(tout.max()) if T else 0) + forest.K
-    return ForestLoco(used, nodes, np.ascontiguousarray(forest.tree_off, np.int64), value, tw, tout, n_out, float(S),
-                      int(forest.missing_bin))
+    return ForestLoco(used, nodes, np.ascontiguousarray(forest.tree_off, np.int64), value, tw, tout,
+                      _columns_needed(forest, tout), _magnitude_bound(forest, tw, value), int(forest.missing_bin))
 
 
 def forest_loco(forest: Forest, Xb: torch.Tensor, zero_bins, rows: Optional[torch.Tensor] = None,
@@ -1670,16 +1685,10 @@ def forest_loco(forest: Forest, Xb: torch.Tensor, zero_bins, rows: Optional[torc
     int64 fixed point, so they agree bit for bit. ``plan``: the prepared :func:`forest_loco_plan` of the same
     forest / weights / columns (callers cache it)."""
     lp = plan if plan is not None else forest_loco_plan(forest, tree_weight, tree_out)
-    C = int(n_out) if n_out is not None else lp.n_out
-    if C < lp.n_out:
-        raise ValueError(f"n_out = {C} but the trees write {lp.n_out} columns")
-    dev = Xb.device
-    Xb = Xb.contiguous()
     if Xb.dtype != torch.uint8 or Xb.dim() != 2:
         raise ValueError("Xb must be a uint8 [N, F] matrix")
-    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
-    if lp.used.size and int(lp.used[-1]) >= F:
-        raise ValueError(f"the forest splits on column {int(lp.used[-1])}, the matrix has {F}")
+    dev = Xb.device
+    Xb, _, F, C, row_list, n, used64 = _explain_rows(lp, Xb, rows, n_out)
     zb = zero_bins.cpu().numpy() if isinstance(zero_bins, torch.Tensor) else np.asarray(zero_bins)
     zb = zb.reshape(-1).astype(np.int32)
     if zb.size != F:
@@ -1695,9 +1704,6 @@ def forest_loco(forest: Forest, Xb: torch.Tensor, zero_bins, rows: Optional[torc
             raise ValueError("groups must be disjoint")
         group_of[cols] = g
     meta = ((zb[lp.used] & 0xFF) | ((group_of[lp.used] + 1) << 8)).astype(np.int32)
-    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
-    n = Nrows if rows is None else int(row_list.numel())
-    used64 = lp.used.astype(np.int64)
     out = torch.empty(n, U + G + 1, C, dtype=torch.float64, device=dev)
     if dev.type == "cuda":
         d = lp.on(dev)
@@ -1707,8 +1713,8 @@ def forest_loco(forest: Forest, Xb: torch.Tensor, zero_bins, rows: Optional[torc
             int(lp.nodes.shape[0]), N.ptr(d[3]), KV, N.ptr(d[4]), N.ptr(d[5]), lp.missing_bin, C, lp.scale,
             N.ptr(out), N.stream(dev))
         if rc == -3:                 # one row's tile beyond the LDS limit
-            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
-            return forest_loco(forest, sub.cpu(), zb, None, glist, n_out=C, plan=lp)[0].to(dev), used64
+            return _on_host_twin(
+                Xb, row_list, lambda sub: forest_loco(forest, sub, zb, None, glist, n_out=C, plan=lp)[0]), used64
         N.check(rc, "forest_loco")
         return out, used64
     N.check(N.host().tmog_forest_loco_cpu(
@@ -1741,16 +1747,10 @@ def forest_partial_dependence(forest: Forest, Xb: torch.Tensor, cols, n_grid: in
     ``_walks`` (host matrices only): an int64 ``[2]`` array that the host twin adds its counts of base walks and of
     step-function walks to (``benchmarks/bench_partial_dependence.py``)."""
     lp = plan if plan is not None else forest_loco_plan(forest, tree_weight, tree_out)
-    C = int(n_out) if n_out is not None else lp.n_out
-    if C < lp.n_out:
-        raise ValueError(f"n_out = {C} but the trees write {lp.n_out} columns")
-    dev = Xb.device
-    Xb = Xb.contiguous()
     if Xb.dtype != torch.uint8 or Xb.dim() != 2:
         raise ValueError("Xb must be a uint8 [N, F] matrix")
-    Nrows, F = int(Xb.shape[0]), int(Xb.shape[1])
-    if lp.used.size and int(lp.used[-1]) >= F:
-        raise ValueError(f"the forest splits on column {int(lp.used[-1])}, the matrix has {F}")
+    dev = Xb.device
+    Xb, Nrows, F, C, row_list, n, used64 = _explain_rows(lp, Xb, rows, n_out)
     NB = int(n_grid)
     if not 1 <= NB <= 256:
         raise ValueError(f"n_grid = {NB}: the grid is the model's histogram width, 1 .. 256")
@@ -1765,8 +1765,6 @@ def forest_partial_dependence(forest: Forest, Xb: torch.Tensor, cols, n_grid: in
     slot_of = np.full(F, -1, np.int32)
     slot_of[cq] = np.arange(Q, dtype=np.int32)
     slot_of_used = np.ascontiguousarray(slot_of[lp.used], np.int32)
-    row_list = None if rows is None else rows.to(dev).to(torch.int32).contiguous()
-    n = Nrows if rows is None else int(row_list.numel())
     if row_list is not None and n and not (0 <= int(row_list.min()) and int(row_list.max()) < Nrows):
         raise ValueError("rows names a row outside the matrix")
     U, T, KV = int(lp.used.size), int(lp.tree_weight.size), int(lp.value.shape[1])
@@ -1783,8 +1781,8 @@ def forest_partial_dependence(forest: Forest, Xb: torch.Tensor, cols, n_grid: in
             int(lp.nodes.shape[0]), N.ptr(d[3]), KV, N.ptr(d[4]), N.ptr(d[5]), lp.missing_bin, C, scale,
             0 if ice else 1, N.ptr(out), N.stream(dev))
         if rc == -3:                 # one row x one column beyond the LDS limit
-            sub = Xb if row_list is None else Xb.index_select(0, row_list.to(torch.long))
-            return forest_partial_dependence(forest, sub.cpu(), cq, NB, None, n_out=C, plan=lp, ice=ice).to(dev)
+            return _on_host_twin(Xb, row_list, lambda sub: forest_partial_dependence(
+                forest, sub, cq, NB, None, n_out=C, plan=lp, ice=ice))
         N.check(rc, "forest_pd")
         return out if ice else out.to(torch.float64) * (1.0 / scale)
     out = torch.empty(shape, dtype=torch.float64)

@@ -213,6 +213,17 @@ int tmog_forest_pd_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_l
                        const int32_t* tree_out, int missing_bin, int C, double scale, int mode, double* out,
                        int64_t* walks);
 
+// ---- host/shap_cpu.cpp: host twins of hip/shap_kernels.hip (same arguments minus the stream), plain fp64 sums
+int tmog_forest_shap_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
+                         int64_t P, const int64_t* p_off, const int32_t* p_out, const double* p_val, int KV,
+                         const double* bias, const int32_t* e_feat, const int32_t* e_rng, const double* e_z,
+                         const int64_t* bin_off, int missing_bin, int C, double scale, double* out);
+int tmog_forest_shap_interactions_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U,
+                                      const int32_t* used, int64_t P, const int64_t* p_off, const int32_t* p_out,
+                                      const double* p_val, int KV, const double* bias, const int32_t* e_feat,
+                                      const int32_t* e_rng, const double* e_z, const int64_t* bin_off,
+                                      int missing_bin, int C, double scale, double* tri);
+
 // ---- host/streaming_histogram.cpp
 void* tmog_shist_new(int max_bins, int max_spool, int64_t round_to);
 void tmog_shist_free(void* h);
@@ -267,15 +278,6 @@ int tmog_forest_staged_eval_cpu(const uint8_t* Xb, int F, const int32_t* row_lis
                                 const int64_t* stage_off, int S, const int32_t* tree_col, int K, int metric,
                                 double scale, int bins, double* margins, double* values, int64_t* counts,
                                 int32_t* tables);
-int tmog_forest_shap_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
-                         int64_t P, const int64_t* p_off, const int32_t* p_out, const double* p_val, int KV,
-                         const double* bias, const int32_t* e_feat, const int32_t* e_rng, const double* e_z,
-                         const int64_t* bin_off, int missing_bin, int C, double scale, double* out);
-int tmog_forest_shap_interactions_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U,
-                                      const int32_t* used, int64_t P, const int64_t* p_off, const int32_t* p_out,
-                                      const double* p_val, int KV, const double* bias, const int32_t* e_feat,
-                                      const int32_t* e_rng, const double* e_z, const int64_t* bin_off,
-                                      int missing_bin, int C, double scale, double* tri);
 int tmog_find_splits_cpu(const double* sample, int64_t S, int F, int max_splits, double* out, int32_t* n_out);
 int64_t tmog_tree_finalize_cpu(int64_t n, int T, const int64_t* tree, const int64_t* feat_in, const int64_t* bin,
                                const uint8_t* dl, const double* gain, const double* tot, int S,

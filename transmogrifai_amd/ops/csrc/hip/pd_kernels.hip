@@ -6,7 +6,7 @@
 //
 // Moving column c of a row can change tree t's answer only if c is tested on the path the row already takes, and
 // below the first such node the answer as a function of the bin is a step function. Per (row, tree) the kernel
-//   1. walks the base path (tmog::goes_left), adds w_t v[leaf0] to the row's base and counts the nodes of the path
+//   1. walks the base path (tmog::walk_to_leaf), adds w_t v[leaf0] to the row's base and counts the nodes of the path
 //      whose column is requested;
 //   2. walks the base path once more; at the FIRST node of every requested column on the path it produces the
 //      column's step function without a stack: starting with bin b = 0 it walks from that node to a leaf, deciding
@@ -16,18 +16,19 @@
 //      The missing bin (the last grid point, when the forest has one) takes one walk of its own along the nodes'
 //      default directions.
 // "Did this column occur higher up" is answered by walking the prefix of the base path again (only from the second
-// requested node of a path on), as loco_kernels.hip does: no per-lane array of path nodes, nothing in scratch.
+// requested node of a path on; tmog::walk_prefix of common/forest_walk.hpp): no per-lane array of path nodes,
+// nothing in scratch.
 //
 // A step [b, hi] that ends in another leaf than the base path is stored as a difference: with
-// d = round(w (v[leaf'] - v[leaf0]) scale), +d at grid slot b and -d at slot hi + 1 (dropped past the last ordinary
-// bin); the missing bin's d goes straight to its slot. The epilogue takes the integer prefix sum over the ordinary
-// bins and adds the base. d is rounded once and added and subtracted as the same integer, so the prefix sums are
-// exact and the result does not depend on any order: bitwise reproducible and equal to the host twin
+// d = tmog::fx_delta(w, v[leaf'], v[leaf0], scale), +d at grid slot b and -d at slot hi + 1 (dropped past the last
+// ordinary bin); the missing bin's d goes straight to its slot. The epilogue takes the integer prefix sum over the
+// ordinary bins and adds the base. d is rounded once and added and subtracted as the same integer, so the prefix
+// sums are exact and the result does not depend on any order: bitwise reproducible and equal to the host twin
 // (host/pd_cpu.cpp).
 //
-// Mapping: as loco_kernels.hip -- a workgroup owns a tile of rows, stages the bins of the used columns of its rows
-// in LDS, its lanes take (row, tree) pairs, rows fastest; nodes are the packed records of forest_loco_plan. The
-// requested columns are chunked over gridDim.y so that the tile fits LDS. Modes:
+// Mapping: the row tile of hip/row_tile.hpp -- a workgroup owns a tile of rows, stages the bins of the used columns
+// of its rows in LDS, its lanes take (row, tree) pairs, rows fastest; nodes are the packed records of
+// common/forest_walk.hpp. The requested columns are chunked over gridDim.y so that the tile fits LDS. Modes:
 //   0 ICE   LDS tile [rows][Qc][NB][C]; stored as fp64 to out[n][Q][NB][C] with plain stores;
 //   1 sum   one [Qc][NB][C] tile per workgroup that all its rows add to (the prefix sum is linear, so summing the
 //           differences first gives the same integers), added to the int64 buffer out[Q][NB][C] with 64-bit global
@@ -46,70 +47,37 @@
 #include <stdint.h>
 
 #include "hip/tmog_hip_abi.h"
-#include "common/tree_rules.hpp"
+#include "hip/row_tile.hpp"
+#include "common/forest_walk.hpp"
 
 namespace {
 
-constexpr int PD_THREADS = 512;
-constexpr int PD_MAX_ROWS = 64;
-constexpr size_t PD_LDS_LIMIT = 160 * 1024;
-constexpr size_t PD_LDS_SHARE = 80 * 1024;   // two workgroups per CU while the tile stays >= 16 rows
+using tmog::kTileThreads;
+using Node = tmog::WalkNode;
 
-struct PdArgs {
-  const uint8_t* Xb;
-  int F;
-  int64_t n;
-  const int32_t* row_list;
-  int U;
-  const int32_t* used;
+struct PdArgs : tmog::RowTile {
   const int32_t* slot_of_used;   // [U] index q of the used column among the requested ones, or -1
   int Q;
   int NB;                        // grid points, the missing bin (last) included
   int NO;                        // ordinary bins: NB, or NB - 1 with a missing bin
   int T;
   const int64_t* tree_off;
-  const int4* nodes;             // (u, bin | default_left << 16, left, right)
+  const Node* nodes;
   const float* value;
   int KV;
   const float* tree_weight;
   const int32_t* tree_out;
-  int missing_bin;
-  int C;
-  double scale;
   int mode;
   void* out;
-  int tile_rows;
   int acc_rows;                  // rows of the LDS tile: tile_rows, or 1 (the sum)
   int qc;                        // requested columns per chunk
-  int ustride;                   // bytes per staged row (U rounded up to 4)
 };
 
-__device__ __forceinline__ bool pd_left(int bin, const int4& nd, int missing_bin) {
-  return tmog::goes_left((uint8_t)bin, nd.y & 0xFFFF, [&] { return (nd.y >> 16) != 0; }, missing_bin);
-}
-
-// The walk from `node` to its leaf for one staged row with slot u's column at bin b; *hi is lowered to the split
-// bin of every node of that column at which the walk turns left.
-__device__ __forceinline__ int pd_walk(const PdArgs& a, const uint8_t* xr, int node, int u, int b, int* hi) {
-  for (;;) {
-    const int4 nd = a.nodes[node];
-    if (nd.z < 0) return node;
-    bool l;
-    if (nd.x == u) {
-      l = pd_left(b, nd, a.missing_bin);
-      if (l) *hi = min(*hi, nd.y & 0xFFFF);
-    } else {
-      l = pd_left(xr[nd.x], nd, a.missing_bin);
-    }
-    node = l ? nd.z : nd.w;
-  }
-}
-
-__global__ void __launch_bounds__(PD_THREADS) forest_pd_kernel(PdArgs a) {
+__global__ void __launch_bounds__(kTileThreads) forest_pd_kernel(PdArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int64_t blk0 = (int64_t)blockIdx.x * a.tile_rows;
+  const int64_t blk0 = tmog::tile_first_row(a);
   if (blk0 >= a.n) return;
-  const int nrow = (int)min((int64_t)a.tile_rows, a.n - blk0);
+  const int nrow = tmog::tile_row_count(a, blk0);
   const int q0 = (int)blockIdx.y * a.qc;
   const int nq = min(a.qc, a.Q - q0);
   const int qstride = a.NB * a.C;                    // one requested column of one row
@@ -119,73 +87,66 @@ __global__ void __launch_bounds__(PD_THREADS) forest_pd_kernel(PdArgs a) {
   unsigned long long* base = acc + nacc;             // [tile_rows][C]
   int32_t* slot = reinterpret_cast<int32_t*>(base + (size_t)a.tile_rows * a.C);
   uint8_t* sbin = reinterpret_cast<uint8_t*>(slot + a.ustride);
-  for (size_t i = threadIdx.x; i < nacc + (size_t)a.tile_rows * a.C; i += PD_THREADS) acc[i] = 0ull;
-  for (int k = threadIdx.x; k < a.U; k += PD_THREADS) {
+  tmog::zero_tile(acc, nacc + (size_t)a.tile_rows * a.C);
+  for (int k = threadIdx.x; k < a.U; k += kTileThreads) {
     const int q = a.slot_of_used[k] - q0;
     slot[k] = (q >= 0 && q < nq) ? q : -1;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < nrow; r += PD_THREADS / 64) {
-    const int64_t row = a.row_list ? a.row_list[blk0 + r] : (blk0 + r);
-    const uint8_t* src = a.Xb + row * (int64_t)a.F;
-    for (int k = lane; k < a.U; k += 64) sbin[(size_t)r * a.ustride + k] = src[a.used[k]];
-  }
+  tmog::stage_used_bins(a, blk0, nrow, sbin);
   __syncthreads();
   const int items = nrow * a.T;
-  for (int it = threadIdx.x; it < items; it += PD_THREADS) {
+  for (int it = threadIdx.x; it < items; it += kTileThreads) {
     const int t = it / nrow, r = it - t * nrow;
     const int root = (int)a.tree_off[t];
     if ((int)a.tree_off[t + 1] <= root) continue;
     const uint8_t* xr = sbin + (size_t)r * a.ustride;
     // 1. the base path
-    int node = root, nreq = 0;
-    for (;;) {
-      const int4 nd = a.nodes[node];
-      if (nd.z < 0) break;
-      nreq += slot[nd.x] >= 0;
-      node = pd_left(xr[nd.x], nd, a.missing_bin) ? nd.z : nd.w;
-    }
-    const int leaf = node;
+    int nreq = 0;
+    const int leaf = tmog::walk_to_leaf(a.nodes, a.missing_bin, root, [&](const Node& nd, int) {
+      nreq += slot[nd.u] >= 0;
+      return (int)xr[nd.u];
+    });
     const double w = (double)a.tree_weight[t];
     const float* v0 = a.value + (size_t)leaf * a.KV;
     const int col = a.tree_out[t];
-    {
-#pragma clang fp contract(off)
-      for (int c = 0; c < a.KV; ++c)
-        atomicAdd(base + (size_t)r * a.C + col + c, (unsigned long long)__double2ll_rn(w * (double)v0[c] * a.scale));
-    }
+    for (int c = 0; c < a.KV; ++c)
+      atomicAdd(base + (size_t)r * a.C + col + c, (unsigned long long)tmog::fx_base(w, v0[c], a.scale));
     if (nreq == 0) continue;
     unsigned long long* tile = acc + (a.acc_rows > 1 ? (size_t)r * rstride : 0) + col;
     // 2. the step function of every requested column from its first node on the path
-    int seen = 0;
-    node = root;
+    int seen = 0, node = root;
     for (;;) {
-      const int4 nd = a.nodes[node];
-      if (nd.z < 0) break;
-      const int q = slot[nd.x];
+      const Node nd = a.nodes[node];
+      if (nd.leaf()) break;
+      const int q = slot[nd.u];
       if (q >= 0) {
-        const int u = nd.x;
+        const int u = nd.u;
         bool seen_u = false;
-        if (seen > 0) {                        // did the column occur higher up on the base path
-          int p = root;
-          while (p != node) {
-            const int4 pd = a.nodes[p];
-            seen_u = seen_u || pd.x == u;
-            p = pd_left(xr[pd.x], pd, a.missing_bin) ? pd.z : pd.w;
-          }
-        }
+        if (seen > 0)                          // did the column occur higher up on the base path
+          tmog::walk_prefix(a.nodes, a.missing_bin, root, node, [&](const Node& pd, int) {
+            seen_u = seen_u || pd.u == u;
+            return (int)xr[pd.u];
+          });
         ++seen;
         if (!seen_u) {
+          // the walk from `node` with column u at bin b; hi is lowered to the split bin of every node of that
+          // column at which the walk turns left
+          auto walk_at = [&](int b, int* hi) {
+            return tmog::walk_to_leaf(a.nodes, a.missing_bin, node, [&](const Node& wd, int) {
+              if (wd.u != u) return (int)xr[wd.u];
+              if (tmog::node_goes_left(b, wd, a.missing_bin)) *hi = min(*hi, wd.split_bin());
+              return b;
+            });
+          };
           unsigned long long* dq = tile + (size_t)q * qstride;
           int b = 0;
           while (b < a.NO) {
             int hi = a.NO - 1;
-            const int other = pd_walk(a, xr, node, u, b, &hi);
+            const int other = walk_at(b, &hi);
             if (other != leaf) {
-#pragma clang fp contract(off)
               const float* v1 = a.value + (size_t)other * a.KV;
               for (int c = 0; c < a.KV; ++c) {
-                const long long d = __double2ll_rn(w * ((double)v1[c] - (double)v0[c]) * a.scale);
+                const long long d = tmog::fx_delta(w, v1[c], v0[c], a.scale);
                 atomicAdd(dq + (size_t)b * a.C + c, (unsigned long long)d);
                 if (hi + 1 < a.NO) atomicAdd(dq + (size_t)(hi + 1) * a.C + c, (unsigned long long)(-d));
               }
@@ -194,26 +155,24 @@ __global__ void __launch_bounds__(PD_THREADS) forest_pd_kernel(PdArgs a) {
           }
           if (a.NO < a.NB) {                   // the missing bin: one walk along the default directions
             int hi = 0;
-            const int other = pd_walk(a, xr, node, u, a.missing_bin, &hi);
+            const int other = walk_at(a.missing_bin, &hi);
             if (other != leaf) {
-#pragma clang fp contract(off)
               const float* v1 = a.value + (size_t)other * a.KV;
               for (int c = 0; c < a.KV; ++c)
-                atomicAdd(dq + (size_t)a.NO * a.C + c,
-                          (unsigned long long)__double2ll_rn(w * ((double)v1[c] - (double)v0[c]) * a.scale));
+                atomicAdd(dq + (size_t)a.NO * a.C + c, (unsigned long long)tmog::fx_delta(w, v1[c], v0[c], a.scale));
             }
           }
         }
         if (seen == nreq) break;               // no requested column below
       }
-      node = pd_left(xr[nd.x], nd, a.missing_bin) ? nd.z : nd.w;
+      node = tmog::node_goes_left(xr[nd.u], nd, a.missing_bin) ? nd.left : nd.right;
     }
   }
   __syncthreads();
   const int live = nq * qstride;               // the tile row's part this chunk uses
   const int nr = a.mode == 0 ? nrow : 1;
   if (a.mode != 0) {                           // the sum's tile is shared already; its rows' bases add up
-    for (int c = threadIdx.x; c < a.C; c += PD_THREADS) {
+    for (int c = threadIdx.x; c < a.C; c += kTileThreads) {
       unsigned long long s = 0ull;
       for (int r = 1; r < nrow; ++r) s += base[(size_t)r * a.C + c];
       base[c] += s;
@@ -222,7 +181,7 @@ __global__ void __launch_bounds__(PD_THREADS) forest_pd_kernel(PdArgs a) {
   }
   // integer prefix sum over the ordinary bins, plus the base
   const int curves = nr * nq * a.C;
-  for (int it = threadIdx.x; it < curves; it += PD_THREADS) {
+  for (int it = threadIdx.x; it < curves; it += kTileThreads) {
     const int r = it / (nq * a.C), rem = it - r * (nq * a.C);
     const int q = rem / a.C, c = rem - q * a.C;
     unsigned long long* p = acc + (size_t)r * rstride + (size_t)q * qstride + c;
@@ -239,13 +198,13 @@ __global__ void __launch_bounds__(PD_THREADS) forest_pd_kernel(PdArgs a) {
     const double inv = 1.0 / a.scale;
     double* o = reinterpret_cast<double*>(a.out);
     const size_t total = (size_t)nrow * live;
-    for (size_t i = threadIdx.x; i < total; i += PD_THREADS) {
+    for (size_t i = threadIdx.x; i < total; i += kTileThreads) {
       const size_t r = i / live, k = i - r * live;
-      o[((size_t)(blk0 + r) * a.Q + q0) * qstride + k] = (double)(long long)acc[r * rstride + k] * inv;
+      o[((size_t)(blk0 + r) * a.Q + q0) * qstride + k] = tmog::tile_value(acc[r * rstride + k], inv);
     }
   } else {
     unsigned long long* o = reinterpret_cast<unsigned long long*>(a.out) + (size_t)q0 * qstride;
-    for (int i = threadIdx.x; i < live; i += PD_THREADS)
+    for (int i = threadIdx.x; i < live; i += kTileThreads)
       if (acc[i] != 0ull) atomicAdd(o + i, acc[i]);
   }
 }
@@ -271,33 +230,29 @@ int tmog_hip_forest_pd(const uint8_t* Xb, int F, int64_t n, const int32_t* row_l
   if (NB < 1 || NB > 256 || mode < 0 || mode > 1) return -1;
   if (missing_bin >= 0 && missing_bin < NB && missing_bin != NB - 1) return -1;
   const int NO = (missing_bin >= 0 && missing_bin < NB) ? NB - 1 : NB;
-  const int ustride = (U + 3) & ~3;
+  const int ustride = tmog::ustride_of(U);
   const int64_t qstride = (int64_t)NB * C;
-  if (qstride * 8 > (int64_t)PD_LDS_LIMIT) return -3;
-  if (pd_lds_bytes(1, 1, 1, qstride, C, ustride) > PD_LDS_LIMIT) return -3;
-  if (n_nodes > 0x7FFFFFFF || T * PD_MAX_ROWS > 0x7FFFFFFF || (int64_t)Q * qstride > 0x7FFFFFFF) return -4;
+  if (qstride * 8 > (int64_t)tmog::kTileLdsLimit) return -3;
+  if (pd_lds_bytes(1, 1, 1, qstride, C, ustride) > tmog::kTileLdsLimit) return -3;
+  if (n_nodes > 0x7FFFFFFF || T * tmog::kTileMaxRows > 0x7FFFFFFF || (int64_t)Q * qstride > 0x7FFFFFFF) return -4;
+  // two dimensions to size, rows and requested columns per chunk: down to 16 rows first, then fewer columns, while
+  // the tile exceeds the two-workgroup share; then fewer rows while it exceeds the limit
   const bool shared = mode == 1;
-  int rows = PD_MAX_ROWS, qc = Q;
+  int rows = tmog::kTileMaxRows, qc = Q;
   auto bytes = [&] { return pd_lds_bytes(rows, shared ? 1 : rows, qc, qstride, C, ustride); };
-  while (bytes() > PD_LDS_SHARE && (rows > 16 || qc > 1)) {
+  while (bytes() > tmog::kTileLdsShare && (rows > 16 || qc > 1)) {
     if (rows > 16) rows >>= 1;
     else qc = (qc + 1) >> 1;
   }
-  while (rows > 1 && bytes() > PD_LDS_LIMIT) rows >>= 1;
-  if (bytes() > PD_LDS_LIMIT) return -3;
+  while (rows > 1 && bytes() > tmog::kTileLdsLimit) rows >>= 1;
+  if (bytes() > tmog::kTileLdsLimit) return -3;
   const int64_t blocks = (n + rows - 1) / rows;
   const int chunks = (Q + qc - 1) / qc;
-  if (blocks > 0x7FFFFFFF || chunks > 65535) return -4;
-  PdArgs a{Xb, F, n, row_list, U, used, slot_of_used, Q, NB, NO, (int)T, tree_off,
-           reinterpret_cast<const int4*>(nodes), value, KV, tree_weight, tree_out, missing_bin, C, scale, mode, out,
-           rows, shared ? 1 : rows, qc, ustride};
-  const size_t lds = bytes();
-  static const bool lds_attr = hipFuncSetAttribute((const void*)forest_pd_kernel,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)PD_LDS_LIMIT) == hipSuccess;   // once per process
-  if (lds > 64 * 1024 && !lds_attr) return -3;
-  hipLaunchKernelGGL(forest_pd_kernel, dim3((unsigned)blocks, (unsigned)chunks), dim3(PD_THREADS), lds, stream, a);
-  return (int)hipGetLastError();
+  if (blocks > 0x7FFFFFFF || chunks > 65535) return -4;   // ahead of launch_lds' -3, as this entry always answered
+  PdArgs a{{Xb, F, n, row_list, U, used, C, scale, missing_bin, rows, ustride}, slot_of_used, Q, NB, NO, (int)T,
+           tree_off, reinterpret_cast<const Node*>(nodes), value, KV, tree_weight, tree_out, mode, out,
+           shared ? 1 : rows, qc};
+  return tmog::launch_lds<forest_pd_kernel>(blocks, chunks, bytes(), stream, a);
 }
 
 }  // extern "C"

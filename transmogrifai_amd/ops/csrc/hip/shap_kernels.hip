@@ -31,37 +31,26 @@
 #include <algorithm>
 
 #include "hip/tmog_hip_abi.h"
+#include "hip/row_tile.hpp"
+#include "common/forest_walk.hpp"
 
 namespace {
 
-constexpr int SHAP_THREADS = 512;
-constexpr int SHAP_MAX_ROWS = 64;
+using tmog::kTileThreads;
+
 constexpr int SHAP_MAX_M = 64;
-constexpr size_t SHAP_LDS_LIMIT = 160 * 1024;
-constexpr size_t SHAP_LDS_SHARE = 80 * 1024;   // two workgroups per CU while the tile stays >= 16 rows
 constexpr int SHAP_RCP = SHAP_MAX_M + 2;       // rcp[k] = 1 / k, k = 1 .. 65
 
-struct ShapArgs {
-  const uint8_t* Xb;
-  int F;
-  int64_t n;
-  const int32_t* row_list;
-  int U;
-  const int32_t* used;
+struct ShapArgs : tmog::RowTile {
   const int64_t* p_off;
   const int32_t* p_out;
   const double* p_val;
   int KV;
   const double* bias;       // [C] sum over paths of value * prod z (row-independent)
   const int32_t* e_feat;
-  const int32_t* e_rng;     // lo | hi << 12 | missing-satisfies << 24
+  const int32_t* e_rng;     // tmog::element_satisfied has the layout
   const double* e_z;
-  int missing_bin;
-  int C;
-  double scale;
   double* out;
-  int tile_rows;
-  int ustride;              // bytes per staged row (U rounded up to 4)
 };
 
 __device__ __forceinline__ size_t shap_acc_elems(int rows, int U, int C) { return (size_t)rows * (U + 1) * C; }
@@ -80,6 +69,59 @@ __device__ __forceinline__ double shap_shift_up(double w, int e) {
   }
 }
 
+// What lane e of group g knows of its element for the group's row r (valid: r is a row of the tile; el: the lane
+// holds an element, of slot u, range word rng and zero fraction z).
+struct ShapRow {
+  bool o;                     // the one fraction: the row satisfies the element (true for lanes without one)
+  bool dead;                  // an unsatisfied element of zero fraction 0 makes the path's game identically 0
+  unsigned long long ones;    // ballot of o over the wave
+};
+__device__ __forceinline__ ShapRow shap_row(const ShapArgs& a, const uint8_t* sbin, int r, bool valid, bool el,
+                                            int u, int rng, double z, unsigned long long gmask) {
+  const int b = (valid && el) ? (int)sbin[(size_t)r * a.ustride + u] : 0;
+  const bool sat = tmog::element_satisfied(rng, b, a.missing_bin);
+  const bool o = !el || sat;
+  const bool dead = (__ballot(el && !sat && z == 0.0) & gmask) != 0;
+  return ShapRow{o, dead, __ballot(o)};
+}
+
+// One EXTEND step: lane e holds w[e]; step s adds an element of zero fraction zl and one fraction ol, rs = 1 / (s + 1).
+template <int W>
+__device__ __forceinline__ double shap_extend(double w, int e, int s, double zl, bool ol, double rs) {
+  const double wp = shap_shift_up<W>(w, e);
+  return (zl * w * (double)(s - e) + (ol ? wp * (double)e : 0.0)) * rs;
+}
+
+// The UNWOUND sum of this lane's element (one fraction o, zero fraction z, invz = 1 / z or 0) over a path of len
+// elements whose weights w[j] sit in lane j of the group; top = w[len], scaled by 1 / (len + 1) as the result is.
+// rcp(k) gives 1 / k from wherever the caller keeps it. The broadcasts do not depend on the running sums: four are
+// kept in flight.
+template <int W, class Rcp>
+__device__ __forceinline__ double shap_unwound(double w, int len, bool o, double z, double invz, double top,
+                                               Rcp rcp) {
+  double next = top, total = 0.0;
+  auto unwind = [&](int j, double wj) {
+    const double rj = rcp(j + 1), rmj = rcp(len - j);
+    if (o) {
+      const double tmp = next * rj;
+      total += tmp;
+      next = wj - tmp * z * (double)(len - j);
+    } else {
+      total += wj * invz * rmj;
+    }
+  };
+  int j = len - 1;
+  for (; j >= 3; j -= 4) {
+    const double w0 = __shfl(w, j, W), w1 = __shfl(w, j - 1, W), w2 = __shfl(w, j - 2, W), w3 = __shfl(w, j - 3, W);
+    unwind(j, w0);
+    unwind(j - 1, w1);
+    unwind(j - 2, w2);
+    unwind(j - 3, w3);
+  }
+  for (; j >= 0; --j) unwind(j, __shfl(w, j, W));
+  return total;
+}
+
 template <int W>
 __device__ __forceinline__ void shap_paths(const ShapArgs& a, int64_t p0, int64_t p1, int nrow,
                                            unsigned long long* acc, const double* rcp, const uint8_t* sbin) {
@@ -87,7 +129,7 @@ __device__ __forceinline__ void shap_paths(const ShapArgs& a, int64_t p0, int64_
   const int lane = threadIdx.x & 63;
   const int e = lane & (W - 1), g = lane / W;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = SHAP_THREADS / 64;
+  const int nwaves = kTileThreads / 64;
   const unsigned long long gmask = (W == 64 ? ~0ull : ((1ull << W) - 1ull)) << (g * W);
   const int slots = (a.U + 1) * a.C;
   for (int64_t p = p0 + wave; p < p1; p += nwaves) {
@@ -98,49 +140,20 @@ __device__ __forceinline__ void shap_paths(const ShapArgs& a, int64_t p0, int64_
     const int rng = el ? a.e_rng[eo + e] : 0;
     const double z = el ? a.e_z[eo + e] : 1.0;
     const double invz = z != 0.0 ? 1.0 / z : 0.0;
-    const int lo = rng & 0xFFF, hi = (rng >> 12) & 0xFFF, miss_ok = (rng >> 24) & 1;
     const int col = a.p_out[p];
     const double* val = a.p_val + p * a.KV;
     const double rtop = rcp[m + 1];
     for (int r0 = 0; r0 < nrow; r0 += G) {
       const int r = r0 + g;
       const bool valid = r < nrow;
-      const int b = (valid && el) ? (int)sbin[(size_t)r * a.ustride + u] : 0;
-      const bool sat = (a.missing_bin >= 0 && b == a.missing_bin) ? (miss_ok != 0) : (lo <= b && b <= hi);
-      const bool o = !el || sat;
-      // an unsatisfied element of zero fraction 0 makes the path's game identically 0 for this row
-      const bool dead = (__ballot(el && !sat && z == 0.0) & gmask) != 0;
-      const unsigned long long ones = __ballot(o);
-      const bool all_one = (~ones & gmask) == 0;
-      // EXTEND: lane e holds w[e], e < m; step l adds element l (held by lane l - 1)
+      const ShapRow row = shap_row(a, sbin, r, valid, el, u, rng, z, gmask);
+      const bool o = row.o, dead = row.dead;
+      const bool all_one = (~row.ones & gmask) == 0;
+      // EXTEND: lane e holds w[e], e < m; step l adds element l - 1; its zero fraction is a wave-uniform load
       double w = e == 0 ? 1.0 : 0.0;
-      for (int l = 1; l <= m; ++l) {
-        const double zl = a.e_z[eo + l - 1];
-        const bool ol = (ones >> (g * W + l - 1)) & 1ull;
-        const double wp = shap_shift_up<W>(w, e);
-        w = (zl * w * (double)(l - e) + (ol ? wp * (double)e : 0.0)) * rcp[l + 1];
-      }
-      // UNWOUND sum of this lane's element (scaled by 1 / (m + 1) until the end)
-      double next = all_one ? rtop : 0.0, total = 0.0;
-      auto unwind = [&](int j, double wj) {
-        if (o) {
-          const double tmp = next * rcp[j + 1];
-          total += tmp;
-          next = wj - tmp * z * (double)(m - j);
-        } else {
-          total += wj * invz * rcp[m - j];
-        }
-      };
-      int j = m - 1;
-      for (; j >= 3; j -= 4) {      // the broadcasts do not depend on the running sums: four in flight
-        const double w0 = __shfl(w, j, W), w1 = __shfl(w, j - 1, W), w2 = __shfl(w, j - 2, W),
-                     w3 = __shfl(w, j - 3, W);
-        unwind(j, w0);
-        unwind(j - 1, w1);
-        unwind(j - 2, w2);
-        unwind(j - 3, w3);
-      }
-      for (; j >= 0; --j) unwind(j, __shfl(w, j, W));
+      for (int l = 1; l <= m; ++l)
+        w = shap_extend<W>(w, e, l, a.e_z[eo + l - 1], (row.ones >> (g * W + l - 1)) & 1ull, rcp[l + 1]);
+      const double total = shap_unwound<W>(w, m, o, z, invz, all_one ? rtop : 0.0, [&](int k) { return rcp[k]; });
       const double phi = total * (double)(m + 1) * ((o ? 1.0 : 0.0) - z);
       if (valid && !dead && el) {
         unsigned long long* dst = acc + (size_t)r * slots;
@@ -151,24 +164,19 @@ __device__ __forceinline__ void shap_paths(const ShapArgs& a, int64_t p0, int64_
   }
 }
 
-__global__ void __launch_bounds__(SHAP_THREADS) forest_shap_kernel(ShapArgs a, int64_t b0, int64_t b1, int64_t b2,
+__global__ void __launch_bounds__(kTileThreads) forest_shap_kernel(ShapArgs a, int64_t b0, int64_t b1, int64_t b2,
                                                                    int64_t b3) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int64_t blk0 = (int64_t)blockIdx.x * a.tile_rows;
+  const int64_t blk0 = tmog::tile_first_row(a);
   if (blk0 >= a.n) return;
-  const int nrow = (int)min((int64_t)a.tile_rows, a.n - blk0);
+  const int nrow = tmog::tile_row_count(a, blk0);
   const size_t nacc = shap_acc_elems(a.tile_rows, a.U, a.C);
   unsigned long long* acc = reinterpret_cast<unsigned long long*>(smem);
   double* rcp = reinterpret_cast<double*>(smem + nacc * 8);
   uint8_t* sbin = smem + nacc * 8 + SHAP_RCP * 8;
-  for (size_t i = threadIdx.x; i < nacc; i += SHAP_THREADS) acc[i] = 0ull;
+  tmog::zero_tile(acc, nacc);
   if (threadIdx.x < SHAP_RCP) rcp[threadIdx.x] = threadIdx.x ? 1.0 / (double)threadIdx.x : 0.0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < nrow; r += SHAP_THREADS / 64) {
-    const int64_t row = a.row_list ? a.row_list[blk0 + r] : (blk0 + r);
-    const uint8_t* src = a.Xb + row * (int64_t)a.F;
-    for (int k = lane; k < a.U; k += 64) sbin[(size_t)r * a.ustride + k] = src[a.used[k]];
-  }
+  tmog::stage_used_bins(a, blk0, nrow, sbin);
   __syncthreads();
   shap_paths<16>(a, b0, b1, nrow, acc, rcp, sbin);
   shap_paths<32>(a, b1, b2, nrow, acc, rcp, sbin);
@@ -178,9 +186,9 @@ __global__ void __launch_bounds__(SHAP_THREADS) forest_shap_kernel(ShapArgs a, i
   const double inv = 1.0 / a.scale;
   double* o = a.out + (size_t)blk0 * (a.U + 1) * a.C;
   const size_t slots = (size_t)(a.U + 1) * a.C, first_bias = (size_t)a.U * a.C;
-  for (size_t i = threadIdx.x; i < nout; i += SHAP_THREADS) {
+  for (size_t i = threadIdx.x; i < nout; i += kTileThreads) {
     const size_t k = i % slots;
-    o[i] = k >= first_bias ? a.bias[k - first_bias] : (double)(long long)acc[i] * inv;
+    o[i] = k >= first_bias ? a.bias[k - first_bias] : tmog::tile_value(acc[i], inv);
   }
 }
 
@@ -229,7 +237,7 @@ __device__ __forceinline__ void shap_pair_paths(const ShapArgs& a, int UB, int c
   const int lane = threadIdx.x & 63;
   const int e = lane & (W - 1), g = lane / W;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = SHAP_THREADS / 64;
+  const int nwaves = kTileThreads / 64;
   const unsigned long long wmask = W == 64 ? ~0ull : ((1ull << W) - 1ull);
   const unsigned long long gmask = wmask << (g * W);
   const size_t rstride = (size_t)UB * a.U * a.C;
@@ -255,7 +263,6 @@ __device__ __forceinline__ void shap_pair_paths(const ShapArgs& a, int UB, int c
       const int rng = el ? a.e_rng[eo + e] : 0;
       const double z = el ? a.e_z[eo + e] : 1.0;
       const double invz = z != 0.0 ? 1.0 / z : 0.0;
-      const int lo = rng & 0xFFF, hi = (rng >> 12) & 0xFFF, miss_ok = (rng >> 24) & 1;
       // the conditioning positions of this chunk: every group holds the same path, group 0's bits serve
       const unsigned long long cond = __ballot(el && u >= c0 && u < c1) & wmask;
       const int col = a.p_out[p];
@@ -264,11 +271,9 @@ __device__ __forceinline__ void shap_pair_paths(const ShapArgs& a, int UB, int c
       for (int r0 = 0; r0 < nrow; r0 += G) {
         const int r = r0 + g;
         const bool valid = r < nrow;
-        const int b = (valid && el) ? (int)sbin[(size_t)r * a.ustride + u] : 0;
-        const bool sat = (a.missing_bin >= 0 && b == a.missing_bin) ? (miss_ok != 0) : (lo <= b && b <= hi);
-        const bool o = !el || sat;
-        const bool dead = (__ballot(el && !sat && z == 0.0) & gmask) != 0;
-        const unsigned long long ones = __ballot(o);
+        const ShapRow row = shap_row(a, sbin, r, valid, el, u, rng, z, gmask);
+        const bool o = row.o, dead = row.dead;
+        const unsigned long long ones = row.ones;
         const double oz = (o ? 1.0 : 0.0) - z;
         for (unsigned long long cm = cond; cm; cm &= cm - 1ull) {
           const int i = __builtin_ctzll(cm);               // wave-uniform
@@ -281,33 +286,11 @@ __device__ __forceinline__ void shap_pair_paths(const ShapArgs& a, int UB, int c
           double w = e == 0 ? 1.0 : 0.0;
           for (int s = 1; s < m; ++s) {
             const int l = s <= i ? s - 1 : s;
-            const double zl = shap_lane(z, l);
-            const bool ol = (ones >> (g * W + l)) & 1ull;
-            const double wp = shap_shift_up<W>(w, e);
-            w = (zl * w * (double)(s - e) + (ol ? wp * (double)e : 0.0)) * shap_lane(rl, s);
+            w = shap_extend<W>(w, e, s, shap_lane(z, l), (ones >> (g * W + l)) & 1ull, shap_lane(rl, s));
           }
           // UNWOUND of this lane's element on the sub-path of m - 1 elements
-          double next = all_one ? rtop : 0.0, total = 0.0;
-          auto unwind = [&](int j, double wj) {
-            const double rj = shap_lane(rl, j), rmj = shap_lane(rl, m - 2 - j);   // 1 / (j + 1), 1 / (m - 1 - j)
-            if (o) {
-              const double tmp = next * rj;
-              total += tmp;
-              next = wj - tmp * z * (double)(m - 1 - j);
-            } else {
-              total += wj * invz * rmj;
-            }
-          };
-          int j = m - 2;
-          for (; j >= 3; j -= 4) {
-            const double w0 = __shfl(w, j, W), w1 = __shfl(w, j - 1, W), w2 = __shfl(w, j - 2, W),
-                         w3 = __shfl(w, j - 3, W);
-            unwind(j, w0);
-            unwind(j - 1, w1);
-            unwind(j - 2, w2);
-            unwind(j - 3, w3);
-          }
-          for (; j >= 0; --j) unwind(j, __shfl(w, j, W));
+          const double total = shap_unwound<W>(w, m - 1, o, z, invz, all_one ? rtop : 0.0,
+                                               [&](int k) { return shap_lane(rl, k - 1); });
           const double pair = total * (double)m * oz * 0.5 * (oi - zi);
           if (valid && !dead && el && u > ui) {            // u > ui: each pair once, and never e == i
             unsigned long long* dst = acc + (size_t)r * rstride + ((size_t)(ui - c0) * a.U + u) * a.C + col;
@@ -321,24 +304,19 @@ __device__ __forceinline__ void shap_pair_paths(const ShapArgs& a, int UB, int c
 }
 
 // a.out is tri [n][U][U][C]; blockIdx.x: row tile, blockIdx.y: chunk of UB conditioning features
-__global__ void __launch_bounds__(SHAP_THREADS) forest_shap_pair_kernel(ShapArgs a, int UB, int64_t b0, int64_t b1,
+__global__ void __launch_bounds__(kTileThreads) forest_shap_pair_kernel(ShapArgs a, int UB, int64_t b0, int64_t b1,
                                                                         int64_t b2, int64_t b3) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int64_t blk0 = (int64_t)blockIdx.x * a.tile_rows;
+  const int64_t blk0 = tmog::tile_first_row(a);
   const int c0 = (int)blockIdx.y * UB;
   if (blk0 >= a.n || c0 >= a.U) return;
-  const int nrow = (int)min((int64_t)a.tile_rows, a.n - blk0);
+  const int nrow = tmog::tile_row_count(a, blk0);
   const int c1 = min(c0 + UB, a.U);
   const size_t nacc = shap_pair_elems(a.tile_rows, UB, a.U, a.C);
   unsigned long long* acc = reinterpret_cast<unsigned long long*>(smem);
   uint8_t* sbin = smem + nacc * 8;
-  for (size_t i = threadIdx.x; i < nacc; i += SHAP_THREADS) acc[i] = 0ull;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < nrow; r += SHAP_THREADS / 64) {
-    const int64_t row = a.row_list ? a.row_list[blk0 + r] : (blk0 + r);
-    const uint8_t* src = a.Xb + row * (int64_t)a.F;
-    for (int k = lane; k < a.U; k += 64) sbin[(size_t)r * a.ustride + k] = src[a.used[k]];
-  }
+  tmog::zero_tile(acc, nacc);
+  tmog::stage_used_bins(a, blk0, nrow, sbin);
   __syncthreads();
   shap_pair_paths<16>(a, UB, c0, c1, b0, b1, nrow, acc, sbin);
   shap_pair_paths<32>(a, UB, c0, c1, b1, b2, nrow, acc, sbin);
@@ -346,11 +324,8 @@ __global__ void __launch_bounds__(SHAP_THREADS) forest_shap_pair_kernel(ShapArgs
   __syncthreads();
   const double inv = 1.0 / a.scale;
   const size_t per = (size_t)(c1 - c0) * a.U * a.C, rstride = (size_t)UB * a.U * a.C;
-  for (int r = 0; r < nrow; ++r) {
-    double* o = a.out + ((size_t)(blk0 + r) * a.U + c0) * a.U * a.C;
-    const unsigned long long* src = acc + (size_t)r * rstride;
-    for (size_t k = threadIdx.x; k < per; k += SHAP_THREADS) o[k] = (double)(long long)src[k] * inv;
-  }
+  for (int r = 0; r < nrow; ++r)
+    tmog::store_tile_fp64(a.out + ((size_t)(blk0 + r) * a.U + c0) * a.U * a.C, acc + (size_t)r * rstride, per, inv);
 }
 
 size_t shap_pair_lds_bytes(int rows, int UB, int U, int C, int ustride) {
@@ -373,23 +348,14 @@ int tmog_hip_forest_shap(const uint8_t* Xb, int F, int64_t n, const int32_t* row
                          hipStream_t stream) {
   if (n == 0) return 0;
   if (bin_off[3] != P) return -2;
-  const int ustride = (U + 3) & ~3;
-  if (shap_lds_bytes(1, U, C, ustride) > SHAP_LDS_LIMIT) return -3;
-  int rows = SHAP_MAX_ROWS;
-  while (rows > 16 && shap_lds_bytes(rows, U, C, ustride) > SHAP_LDS_SHARE) rows >>= 1;
-  while (rows > 1 && shap_lds_bytes(rows, U, C, ustride) > SHAP_LDS_LIMIT) rows >>= 1;
-  ShapArgs a{Xb, F, n, row_list, U, used, p_off, p_out, p_val, KV, bias, e_feat, e_rng, e_z, missing_bin, C,
-             scale, out, rows, ustride};
-  const size_t lds = shap_lds_bytes(rows, U, C, ustride);
-  static const bool lds_attr = hipFuncSetAttribute((const void*)forest_shap_kernel,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)SHAP_LDS_LIMIT) == hipSuccess;   // once per process
-  if (lds > 64 * 1024 && !lds_attr) return -3;
-  const int64_t blocks = (n + rows - 1) / rows;
-  if (blocks > 0x7FFFFFFF) return -4;
-  hipLaunchKernelGGL(forest_shap_kernel, dim3((unsigned)blocks), dim3(SHAP_THREADS), lds, stream, a, bin_off[0],
-                     bin_off[1], bin_off[2], bin_off[3]);
-  return (int)hipGetLastError();
+  const int ustride = tmog::ustride_of(U);
+  auto bytes = [&](int rows) { return shap_lds_bytes(rows, U, C, ustride); };
+  if (bytes(1) > tmog::kTileLdsLimit) return -3;
+  const int rows = tmog::pick_tile_rows(bytes);
+  ShapArgs a{{Xb, F, n, row_list, U, used, C, scale, missing_bin, rows, ustride}, p_off, p_out, p_val, KV, bias,
+             e_feat, e_rng, e_z, out};
+  return tmog::launch_lds<forest_shap_kernel>((n + rows - 1) / rows, 1, bytes(rows), stream, a, bin_off[0],
+                                              bin_off[1], bin_off[2], bin_off[3]);
 }
 
 // Pair sums of the SHAP interaction values: tri[i][U][U][C] (fp64, every cell written), the unordered pair of
@@ -404,29 +370,21 @@ int tmog_hip_forest_shap_interactions(const uint8_t* Xb, int F, int64_t n, const
                                       int missing_bin, int C, double scale, double* tri, hipStream_t stream) {
   if (n == 0 || U == 0) return 0;
   if (bin_off[3] != P) return -2;
-  const int ustride = (U + 3) & ~3;
-  if (shap_pair_lds_bytes(1, 1, U, C, ustride) > SHAP_LDS_LIMIT) return -3;
-  size_t budget = SHAP_LDS_SHARE;
+  const int ustride = tmog::ustride_of(U);
+  auto bytes = [&](int rows, int UB) { return shap_pair_lds_bytes(rows, UB, U, C, ustride); };
+  if (bytes(1, 1) > tmog::kTileLdsLimit) return -3;
+  size_t budget = tmog::kTileLdsShare;
   int rows = 8;
-  while (rows > 1 && shap_pair_lds_bytes(rows, 1, U, C, ustride) > budget) rows >>= 1;
-  if (shap_pair_lds_bytes(rows, 1, U, C, ustride) > budget) budget = SHAP_LDS_LIMIT;   // rows == 1
+  while (rows > 1 && bytes(rows, 1) > budget) rows >>= 1;
+  if (bytes(rows, 1) > budget) budget = tmog::kTileLdsLimit;   // rows == 1
   const size_t unit = (size_t)rows * U * C * 8;
-  int UB = (int)std::min<size_t>((size_t)U, (budget - (size_t)rows * ustride) / unit);
+  const int UB = (int)std::min<size_t>((size_t)U, (budget - (size_t)rows * ustride) / unit);
   if (UB == U)
-    while (rows < SHAP_MAX_ROWS && shap_pair_lds_bytes(rows * 2, U, U, C, ustride) <= SHAP_LDS_SHARE) rows <<= 1;
-  ShapArgs a{Xb, F, n, row_list, U, used, p_off, p_out, p_val, KV, bias, e_feat, e_rng, e_z, missing_bin, C,
-             scale, tri, rows, ustride};
-  const size_t lds = shap_pair_lds_bytes(rows, UB, U, C, ustride);
-  static const bool lds_attr = hipFuncSetAttribute((const void*)forest_shap_pair_kernel,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)SHAP_LDS_LIMIT) == hipSuccess;   // once per process
-  if (lds > 64 * 1024 && !lds_attr) return -3;
-  const int64_t blocks = (n + rows - 1) / rows;
-  const int chunks = (U + UB - 1) / UB;
-  if (blocks > 0x7FFFFFFF || chunks > 65535) return -4;
-  hipLaunchKernelGGL(forest_shap_pair_kernel, dim3((unsigned)blocks, (unsigned)chunks), dim3(SHAP_THREADS), lds,
-                     stream, a, UB, bin_off[0], bin_off[1], bin_off[2], bin_off[3]);
-  return (int)hipGetLastError();
+    while (rows < tmog::kTileMaxRows && bytes(rows * 2, U) <= tmog::kTileLdsShare) rows <<= 1;
+  ShapArgs a{{Xb, F, n, row_list, U, used, C, scale, missing_bin, rows, ustride}, p_off, p_out, p_val, KV, bias,
+             e_feat, e_rng, e_z, tri};
+  return tmog::launch_lds<forest_shap_pair_kernel>((n + rows - 1) / rows, (U + UB - 1) / UB, bytes(rows, UB), stream,
+                                                   a, UB, bin_off[0], bin_off[1], bin_off[2], bin_off[3]);
 }
 
 }  // extern "C"

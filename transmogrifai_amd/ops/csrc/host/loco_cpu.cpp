@@ -1,38 +1,17 @@
 // Host twin of ../hip/loco_kernels.hip: exact leave-one-column-out sums of a flat forest by path perturbation.
 //
-// Same contract and the same fixed-point rounding as the kernel (its header has the rule and the bound of the
-// scale): every contribution is formed in fp64 from the fp32 tree weight and leaf values, scaled by the power of
-// two `scale`, rounded to int64 and summed as integers, so the result does not depend on the order of the trees
-// and equals the device's bit for bit. Rows are independent (OpenMP).
-#include <cmath>
+// Same contract and the same fixed-point rounding as the kernel (its header has the algorithm and the bound of the
+// scale, common/forest_walk.hpp the node record, the walk and the rounding rule): the contributions are summed as
+// integers, so the result does not depend on the order of the trees and equals the device's bit for bit. Rows are
+// independent (OpenMP).
 #include <cstdint>
 #include <vector>
 #include <omp.h>
 
 #include "common/tmog_abi.h"
-#include "common/tree_rules.hpp"
+#include "common/forest_walk.hpp"
 
-namespace {
-
-struct LocoForest {
-  const int32_t* nodes;   // [.][4]: used slot u | split bin + (default_left << 16) | left | right (left < 0: leaf)
-  const int32_t* meta;    // [U]: zero bin + ((group + 1) << 8)
-  int missing_bin;
-};
-
-// The walk from `node` down to its leaf; over(u) says whether slot u's column is replaced by its zero bin.
-template <class Over>
-inline int64_t loco_walk(const LocoForest& f, const uint8_t* xr, const int32_t* used, int64_t node, Over over) {
-  for (;;) {
-    const int32_t* nd = f.nodes + node * 4;
-    if (nd[2] < 0) return node;
-    const int u = nd[0];
-    const uint8_t b = over(u) ? (uint8_t)(f.meta[u] & 0xFF) : xr[used[u]];
-    node = tmog::goes_left(b, nd[1] & 0xFFFF, [&] { return (nd[1] >> 16) != 0; }, f.missing_bin) ? nd[2] : nd[3];
-  }
-}
-
-}  // namespace
+using Node = tmog::WalkNode;
 
 extern "C" {
 
@@ -40,14 +19,13 @@ int tmog_forest_loco_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row
                          const int32_t* slot_meta, int G, int64_t T, const int64_t* tree_off, const int32_t* nodes,
                          const float* value, int KV, const float* tree_weight, const int32_t* tree_out,
                          int missing_bin, int C, double scale, double* out) {
-  const LocoForest f{nodes, slot_meta, missing_bin};
+  const Node* nd = reinterpret_cast<const Node*>(nodes);
   const int64_t slots = (int64_t)(U + G + 1) * C;
   const double inv = 1.0 / scale;
 #pragma omp parallel
   {
     std::vector<int64_t> acc(slots);
-    std::vector<int64_t> path;      // internal nodes of the base path
-    std::vector<uint8_t> flip;
+    std::vector<int64_t> path;      // the flipped internal nodes of the base path
 #pragma omp for schedule(static)
     for (int64_t i = 0; i < n; ++i) {
       const int64_t row = row_list ? row_list[i] : i;
@@ -56,44 +34,35 @@ int tmog_forest_loco_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row
       for (int64_t t = 0; t < T; ++t) {
         if (tree_off[t + 1] <= tree_off[t]) continue;
         path.clear();
-        flip.clear();
-        int64_t node = tree_off[t];
-        for (;;) {
-          const int32_t* nd = nodes + node * 4;
-          if (nd[2] < 0) break;
-          const int u = nd[0], sb = nd[1] & 0xFFFF;
-          auto dl = [&] { return (nd[1] >> 16) != 0; };
-          const bool l = tmog::goes_left(xr[used[u]], sb, dl, missing_bin);
-          const bool lz = tmog::goes_left((uint8_t)(slot_meta[u] & 0xFF), sb, dl, missing_bin);
-          path.push_back(node);
-          flip.push_back(l != lz);
-          node = l ? nd[2] : nd[3];
-        }
-        const int64_t leaf = node;
+        const int64_t leaf = tmog::walk_to_leaf(nd, missing_bin, tree_off[t], [&](const Node& x, int64_t node) {
+          const int b = xr[used[x.u]];
+          if (tmog::node_goes_left(b, x, missing_bin) != tmog::node_goes_left(slot_meta[x.u] & 0xFF, x, missing_bin))
+            path.push_back(node);
+          return b;
+        });
         const double w = (double)tree_weight[t];
         const float* v0 = value + leaf * KV;
         const int64_t col = tree_out[t];
-        for (int c = 0; c < KV; ++c)
-          acc[(int64_t)(U + G) * C + col + c] += std::llrint(w * (double)v0[c] * scale);
-        auto add = [&](int64_t slot, int64_t other) {
+        for (int c = 0; c < KV; ++c) acc[(int64_t)(U + G) * C + col + c] += tmog::fx_base(w, v0[c], scale);
+        // the walk from `node` with the zero bin at the slots that over(u) names, added to `slot` if it ends elsewhere
+        auto add = [&](int64_t slot, int64_t node, auto over) {
+          const int64_t other = tmog::walk_to_leaf(nd, missing_bin, node, [&](const Node& x, int64_t) {
+            return over(x.u) ? (slot_meta[x.u] & 0xFF) : (int)xr[used[x.u]];
+          });
           if (other == leaf) return;
           const float* v1 = value + other * KV;
-          for (int c = 0; c < KV; ++c)
-            acc[slot * C + col + c] += std::llrint(w * ((double)v1[c] - (double)v0[c]) * scale);
+          for (int c = 0; c < KV; ++c) acc[slot * C + col + c] += tmog::fx_delta(w, v1[c], v0[c], scale);
         };
         for (size_t k = 0; k < path.size(); ++k) {
-          if (!flip[k]) continue;
-          const int u = nodes[path[k] * 4], g = (slot_meta[u] >> 8) - 1;
+          const int u = nd[path[k]].u, g = (slot_meta[u] >> 8) - 1;
           bool seen_u = false, seen_g = false;      // a candidate is counted once, from its first flipped node
           for (size_t j = 0; j < k; ++j) {
-            if (!flip[j]) continue;
-            const int uj = nodes[path[j] * 4];
+            const int uj = nd[path[j]].u;
             seen_u = seen_u || uj == u;
             seen_g = seen_g || (g >= 0 && (slot_meta[uj] >> 8) - 1 == g);
           }
-          if (!seen_u) add(u, loco_walk(f, xr, used, path[k], [&](int x) { return x == u; }));
-          if (g >= 0 && !seen_g)
-            add(U + g, loco_walk(f, xr, used, path[k], [&](int x) { return (slot_meta[x] >> 8) - 1 == g; }));
+          if (!seen_u) add(u, path[k], [&](int x) { return x == u; });
+          if (g >= 0 && !seen_g) add(U + g, path[k], [&](int x) { return (slot_meta[x] >> 8) - 1 == g; });
         }
       }
       double* o = out + i * slots;

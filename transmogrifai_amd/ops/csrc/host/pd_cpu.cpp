@@ -1,49 +1,20 @@
 // Host twin of ../hip/pd_kernels.hip: exact partial dependence / ICE curves of a flat forest over the complete bin
 // grid of the requested columns, by one step function per (row, tree, requested column on the row's path).
 //
-// Same contract and the same integers as the kernel (its header has the algorithm, the rounding rule and the bound
-// of the scale): a step that ends in another leaf than the base path adds d = round(w (v' - v0) scale) at its
-// first bin and -d past its last, the epilogue takes the integer prefix sum and adds the base, so the result does
-// not depend on any order and equals the device's bit for bit. Rows are independent (OpenMP); the sum mode adds
-// the rows' differences per thread and merges the threads' integers.
-#include <cmath>
+// Same contract and the same integers as the kernel (its header has the algorithm and the bound of the scale,
+// common/forest_walk.hpp the node record, the walk and the rounding rule): a step that ends in another leaf than
+// the base path adds d = fx_delta(w, v', v0, scale) at its first bin and -d past its last, the epilogue takes the
+// integer prefix sum and adds the base, so the result does not depend on any order and equals the device's bit
+// for bit. Rows are independent (OpenMP); the sum mode adds the rows' differences per thread and merges the
+// threads' integers.
 #include <cstdint>
 #include <vector>
 #include <omp.h>
 
 #include "common/tmog_abi.h"
-#include "common/tree_rules.hpp"
+#include "common/forest_walk.hpp"
 
-namespace {
-
-struct PdForest {
-  const int32_t* nodes;   // [.][4]: used slot u | split bin + (default_left << 16) | left | right (left < 0: leaf)
-  const int32_t* used;
-  int missing_bin;
-};
-
-inline bool pd_left(uint8_t bin, const int32_t* nd, int missing_bin) {
-  return tmog::goes_left(bin, nd[1] & 0xFFFF, [&] { return (nd[1] >> 16) != 0; }, missing_bin);
-}
-
-// The walk from `node` to its leaf with slot u's column at bin b; *hi is lowered to the split bin of every node of
-// that column at which the walk turns left.
-inline int64_t pd_walk(const PdForest& f, const uint8_t* xr, int64_t node, int u, int b, int* hi) {
-  for (;;) {
-    const int32_t* nd = f.nodes + node * 4;
-    if (nd[2] < 0) return node;
-    bool l;
-    if (nd[0] == u) {
-      l = pd_left((uint8_t)b, nd, f.missing_bin);
-      if (l && (nd[1] & 0xFFFF) < *hi) *hi = nd[1] & 0xFFFF;
-    } else {
-      l = pd_left(xr[f.used[nd[0]]], nd, f.missing_bin);
-    }
-    node = l ? nd[2] : nd[3];
-  }
-}
-
-}  // namespace
+using Node = tmog::WalkNode;
 
 extern "C" {
 
@@ -56,7 +27,7 @@ int tmog_forest_pd_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_l
   if (NB < 1 || NB > 256) return -1;
   if (missing_bin >= 0 && missing_bin < NB && missing_bin != NB - 1) return -1;
   const int NO = (missing_bin >= 0 && missing_bin < NB) ? NB - 1 : NB;
-  const PdForest f{nodes, used, missing_bin};
+  const Node* nd = reinterpret_cast<const Node*>(nodes);
   const int64_t qstride = (int64_t)NB * C, total = (int64_t)Q * qstride;
   const double inv = 1.0 / scale;
   std::vector<int64_t> sum(mode != 0 ? total + C : 0, 0);   // the merged differences, then the bases
@@ -91,37 +62,42 @@ int tmog_forest_pd_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_l
       for (int64_t t = 0; t < T; ++t) {
         if (tree_off[t + 1] <= tree_off[t]) continue;
         path.clear();
-        int64_t node = tree_off[t];
-        for (;;) {
-          const int32_t* nd = nodes + node * 4;
-          if (nd[2] < 0) break;
+        const int64_t leaf = tmog::walk_to_leaf(nd, missing_bin, tree_off[t], [&](const Node& x, int64_t node) {
           path.push_back(node);
-          node = pd_left(xr[used[nd[0]]], nd, missing_bin) ? nd[2] : nd[3];
-        }
+          return (int)xr[used[x.u]];
+        });
         ++n_base;
-        const int64_t leaf = node;
         const double w = (double)tree_weight[t];
         const float* v0 = value + leaf * KV;
         const int64_t col = tree_out[t];
         for (int c = 0; c < KV; ++c)
-          base[col + c] = (int64_t)((uint64_t)base[col + c] + (uint64_t)std::llrint(w * (double)v0[c] * scale));
+          base[col + c] = (int64_t)((uint64_t)base[col + c] + (uint64_t)tmog::fx_base(w, v0[c], scale));
         auto add = [&](int64_t at, int c, int64_t d) { acc[at + c] = (int64_t)((uint64_t)acc[at + c] + (uint64_t)d); };
         for (size_t k = 0; k < path.size(); ++k) {
-          const int u = nodes[path[k] * 4], q = slot_of_used[u];
+          const int u = nd[path[k]].u, q = slot_of_used[u];
           if (q < 0) continue;
           bool seen_u = false;            // a column is handled once, at its first node on the path
-          for (size_t j = 0; j < k && !seen_u; ++j) seen_u = nodes[path[j] * 4] == u;
+          for (size_t j = 0; j < k && !seen_u; ++j) seen_u = nd[path[j]].u == u;
           if (seen_u) continue;
+          // the walk from the node with column u at bin b; hi is lowered to the split bin of every node of that
+          // column at which the walk turns left
+          auto walk_at = [&](int b, int* hi) {
+            ++n_step;
+            return tmog::walk_to_leaf(nd, missing_bin, path[k], [&](const Node& x, int64_t) {
+              if (x.u != u) return (int)xr[used[x.u]];
+              if (tmog::node_goes_left(b, x, missing_bin) && x.split_bin() < *hi) *hi = x.split_bin();
+              return b;
+            });
+          };
           const int64_t dq = q * qstride + col;
           int b = 0;
           while (b < NO) {
             int hi = NO - 1;
-            const int64_t other = pd_walk(f, xr, path[k], u, b, &hi);
-            ++n_step;
+            const int64_t other = walk_at(b, &hi);
             if (other != leaf) {
               const float* v1 = value + other * KV;
               for (int c = 0; c < KV; ++c) {
-                const int64_t d = std::llrint(w * ((double)v1[c] - (double)v0[c]) * scale);
+                const int64_t d = tmog::fx_delta(w, v1[c], v0[c], scale);
                 add(dq + (int64_t)b * C, c, d);
                 if (hi + 1 < NO) add(dq + (int64_t)(hi + 1) * C, c, (int64_t)(0 - (uint64_t)d));
               }
@@ -130,12 +106,11 @@ int tmog_forest_pd_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_l
           }
           if (NO < NB) {                  // the missing bin: one walk along the default directions
             int hi = 0;
-            const int64_t other = pd_walk(f, xr, path[k], u, missing_bin, &hi);
-            ++n_step;
+            const int64_t other = walk_at(missing_bin, &hi);
             if (other != leaf) {
               const float* v1 = value + other * KV;
               for (int c = 0; c < KV; ++c)
-                add(dq + (int64_t)NO * C, c, std::llrint(w * ((double)v1[c] - (double)v0[c]) * scale));
+                add(dq + (int64_t)NO * C, c, tmog::fx_delta(w, v1[c], v0[c], scale));
             }
           }
         }

@@ -294,164 +294,6 @@ int tmog_forest_staged_eval_cpu(const uint8_t* Xb, int F, const int32_t* row_lis
   return 0;
 }
 
-// ----------------------------------------------------------------------------------------- TreeSHAP
-// Host twin of ../hip/shap_kernels.hip (same arguments minus the stream; path layout in
-// models/tree_engine.py forest_paths): exact path-dependent TreeSHAP over merged leaf paths in fp64.
-// For one (row, path) with elements e < m of zero fraction z_e and one fraction o_e in {0, 1}: EXTEND builds
-// the permutation weights w[0..m], UNWOUND gives each element's sum, phi_e += v * (o_e - z_e) * sum_e and
-// the bias slot U gets the row-independent bias[C] (sum of v * prod z). Rows are independent (OpenMP), paths are summed in path order.
-int tmog_forest_shap_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
-                         int64_t P, const int64_t* p_off, const int32_t* p_out, const double* p_val, int KV,
-                         const double* bias, const int32_t* e_feat, const int32_t* e_rng, const double* e_z,
-                         const int64_t* bin_off, int missing_bin, int C, double scale, double* out) {
-  (void)bin_off;
-  (void)scale;
-  int64_t max_m = 0;
-  for (int64_t p = 0; p < P; ++p) max_m = std::max(max_m, p_off[p + 1] - p_off[p]);
-  const int64_t slots = (int64_t)(U + 1) * C;
-#pragma omp parallel
-  {
-    std::vector<double> w(max_m + 1);
-    std::vector<uint8_t> one(max_m + 1);
-#pragma omp for schedule(static)
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t row = row_list ? row_list[i] : i;
-      const uint8_t* xr = Xb + row * (int64_t)F;
-      double* o = out + i * slots;
-      for (int64_t k = 0; k < slots; ++k) o[k] = 0.0;
-      for (int c = 0; c < C; ++c) o[(int64_t)U * C + c] = bias[c];
-      for (int64_t p = 0; p < P; ++p) {
-        const int64_t eo = p_off[p];
-        const int m = (int)(p_off[p + 1] - eo);
-        bool dead = false;
-        for (int e = 0; e < m; ++e) {
-          const int rng = e_rng[eo + e];
-          const int lo = rng & 0xFFF, hi = (rng >> 12) & 0xFFF;
-          const int b = xr[used[e_feat[eo + e]]];
-          const bool sat = (missing_bin >= 0 && b == missing_bin) ? ((rng >> 24) & 1) != 0 : (lo <= b && b <= hi);
-          one[e] = sat;
-          dead = dead || (!sat && e_z[eo + e] == 0.0);
-        }
-        if (dead) continue;      // the path's game is identically 0 for this row
-        const double* val = p_val + p * KV;
-        double* oc = o + p_out[p];
-        if (m == 0) continue;
-        w[0] = 1.0;
-        for (int l = 1; l <= m; ++l) {
-          const double z = e_z[eo + l - 1];
-          const bool ol = one[l - 1];
-          w[l] = 0.0;
-          for (int k = l - 1; k >= 0; --k) {
-            if (ol) w[k + 1] += w[k] * (double)(k + 1) / (double)(l + 1);
-            w[k] = z * w[k] * (double)(l - k) / (double)(l + 1);
-          }
-        }
-        for (int e = 0; e < m; ++e) {
-          const double z = e_z[eo + e];
-          double total = 0.0;
-          if (one[e]) {
-            double next = w[m];
-            for (int j = m - 1; j >= 0; --j) {
-              const double tmp = next / (double)(j + 1);
-              total += tmp;
-              next = w[j] - tmp * z * (double)(m - j);
-            }
-          } else {
-            for (int j = m - 1; j >= 0; --j) total += w[j] / z / (double)(m - j);
-          }
-          const double phi = total * (double)(m + 1) * ((one[e] ? 1.0 : 0.0) - z);
-          double* of = oc + (int64_t)e_feat[eo + e] * C;
-          for (int c = 0; c < KV; ++c) of[c] += phi * val[c];
-        }
-      }
-    }
-  }
-  return 0;
-}
-
-// Host twin of the interaction kernel of ../hip/shap_kernels.hip (same arguments minus the stream): for two
-// elements i != j of a path, Phi_ij = 1/2 * (o_i - z_i) * phi_j(path without i), phi_j the TreeSHAP value on the
-// m - 1 other elements. tri is [n][U][U][C], every cell written; the unordered pair of compact features u < v is
-// counted once, in cell (u, v). Plain fp64 sums in path order; rows are independent (OpenMP).
-int tmog_forest_shap_interactions_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U,
-                                      const int32_t* used, int64_t P, const int64_t* p_off, const int32_t* p_out,
-                                      const double* p_val, int KV, const double* bias, const int32_t* e_feat,
-                                      const int32_t* e_rng, const double* e_z, const int64_t* bin_off,
-                                      int missing_bin, int C, double scale, double* tri) {
-  (void)bias;
-  (void)bin_off;
-  (void)scale;
-  int64_t max_m = 0;
-  for (int64_t p = 0; p < P; ++p) max_m = std::max(max_m, p_off[p + 1] - p_off[p]);
-  const int64_t slots = (int64_t)U * U * C;
-#pragma omp parallel
-  {
-    std::vector<double> w(max_m + 1);
-    std::vector<uint8_t> one(max_m + 1);
-    std::vector<int> sub(max_m + 1);
-#pragma omp for schedule(static)
-    for (int64_t r = 0; r < n; ++r) {
-      const int64_t row = row_list ? row_list[r] : r;
-      const uint8_t* xr = Xb + row * (int64_t)F;
-      double* o = tri + r * slots;
-      for (int64_t k = 0; k < slots; ++k) o[k] = 0.0;
-      for (int64_t p = 0; p < P; ++p) {
-        const int64_t eo = p_off[p];
-        const int m = (int)(p_off[p + 1] - eo);
-        if (m < 2) continue;
-        bool dead = false;
-        for (int e = 0; e < m; ++e) {
-          const int rng = e_rng[eo + e];
-          const int lo = rng & 0xFFF, hi = (rng >> 12) & 0xFFF;
-          const int b = xr[used[e_feat[eo + e]]];
-          const bool sat = (missing_bin >= 0 && b == missing_bin) ? ((rng >> 24) & 1) != 0 : (lo <= b && b <= hi);
-          one[e] = sat;
-          dead = dead || (!sat && e_z[eo + e] == 0.0);
-        }
-        if (dead) continue;      // the path's game is identically 0 for this row
-        const double* val = p_val + p * KV;
-        const int ms = m - 1;    // the sub-path without the conditioning element
-        for (int i = 0; i < m; ++i) {
-          const int ui = e_feat[eo + i];
-          const double fi = 0.5 * ((one[i] ? 1.0 : 0.0) - e_z[eo + i]);
-          for (int k = 0; k < ms; ++k) sub[k] = k < i ? k : k + 1;
-          w[0] = 1.0;
-          for (int l = 1; l <= ms; ++l) {
-            const double z = e_z[eo + sub[l - 1]];
-            const bool ol = one[sub[l - 1]];
-            w[l] = 0.0;
-            for (int k = l - 1; k >= 0; --k) {
-              if (ol) w[k + 1] += w[k] * (double)(k + 1) / (double)(l + 1);
-              w[k] = z * w[k] * (double)(l - k) / (double)(l + 1);
-            }
-          }
-          for (int s = 0; s < ms; ++s) {
-            const int e = sub[s];
-            const int ue = e_feat[eo + e];
-            if (ue <= ui) continue;              // each pair once, from its smaller feature
-            const double z = e_z[eo + e];
-            double total = 0.0;
-            if (one[e]) {
-              double next = w[ms];
-              for (int j = ms - 1; j >= 0; --j) {
-                const double tmp = next / (double)(j + 1);
-                total += tmp;
-                next = w[j] - tmp * z * (double)(ms - j);
-              }
-            } else {
-              for (int j = ms - 1; j >= 0; --j) total += w[j] / z / (double)(ms - j);
-            }
-            const double pair = fi * total * (double)(ms + 1) * ((one[e] ? 1.0 : 0.0) - z);
-            double* oc = o + ((int64_t)ui * U + ue) * C + p_out[p];
-            for (int c = 0; c < KV; ++c) oc[c] += pair * val[c];
-          }
-        }
-      }
-    }
-  }
-  return 0;
-}
-
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------- split finding
