@@ -10,7 +10,10 @@
 // Pass 2 (rff_hist): per column `bins`-bin histogram with the reference bucketing (bins-1 regular
 //   buckets over [min, min + step*(bins-1)), step = (max-min)/(bins-2), Left inclusion, last bucket =
 //   out of range); min == max -> 2 buckets (== max, != max). Workgroup-private LDS histogram, one
-//   global atomic per non-empty LDS bin.
+//   global atomic per non-empty LDS bin. Every split is the reference's `min + step * b`: a rounded multiply, then a
+//   rounded add (split_at), never a fused multiply-add, whose last bit moves values that sit on a split.
+// An empty column has min = +inf and max = -inf; a NaN among the valid values propagates into min and max
+//   (nan_min / nan_max), as the host path and the JVM's math.min / math.max do.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <float.h>
@@ -34,13 +37,23 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// min / max that keep a NaN from either side (fmin / fmax drop it)
+__device__ __forceinline__ double nan_min(double a, double b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
 __device__ __forceinline__ double wave_min(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  for (int o = 32; o > 0; o >>= 1) v = nan_min(v, __shfl_xor(v, o, 64));
   return v;
 }
 __device__ __forceinline__ double wave_max(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// Split b of a histogram, `mn + step * b` with both roundings (hipcc contracts by default).
+__device__ __forceinline__ double split_at(double mn, double step, int b) {
+#pragma clang fp contract(off)
+  const double p = step * (double)b;
+  return mn + p;
 }
 
 __global__ void __launch_bounds__(256) rff_summary_kernel(const void* const* __restrict__ vals,
@@ -54,14 +67,14 @@ __global__ void __launch_bounds__(256) rff_summary_kernel(const void* const* __r
   const void* v = vals[f];
   const uint8_t* ok = valid[f];
   const int dt = dtype[f];
-  double c = 0, nul = 0, mn = DBL_MAX, mx = -DBL_MAX, s1 = 0, s2 = 0, s3 = 0, s4 = 0, sln = 0;
+  double c = 0, nul = 0, mn = INFINITY, mx = -INFINITY, s1 = 0, s2 = 0, s3 = 0, s4 = 0, sln = 0;
   for (int64_t r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
     const bool good = ok == nullptr || ok[r] != 0;
     if (good) {
       const double x = load_val(v, dt, r);
       const double x2 = x * x;
       c += 1; s1 += x; s2 += x2; s3 += x2 * x; s4 += x2 * x2;
-      mn = fmin(mn, x); mx = fmax(mx, x);
+      mn = nan_min(mn, x); mx = nan_max(mx, x);
     } else {
       nul += 1;
       if (label) sln += load_val(label, label_dt, r);
@@ -79,8 +92,8 @@ __global__ void __launch_bounds__(256) rff_summary_kernel(const void* const* __r
   if (threadIdx.x == 0) {
     const int nw = blockDim.x >> 6;
     for (int k = 1; k < nw; ++k) {
-      sh[0][0] += sh[k][0]; sh[0][1] += sh[k][1]; sh[0][2] = fmin(sh[0][2], sh[k][2]);
-      sh[0][3] = fmax(sh[0][3], sh[k][3]);
+      sh[0][0] += sh[k][0]; sh[0][1] += sh[k][1]; sh[0][2] = nan_min(sh[0][2], sh[k][2]);
+      sh[0][3] = nan_max(sh[0][3], sh[k][3]);
       for (int s = 4; s < NSTAT; ++s) sh[0][s] += sh[k][s];
     }
     double* p = part + ((int64_t)f * gridDim.x + blockIdx.x) * NSTAT;
@@ -91,10 +104,10 @@ __global__ void __launch_bounds__(256) rff_summary_kernel(const void* const* __r
 __global__ void rff_summary_fold_kernel(const double* __restrict__ part, int chunks, int F, double* __restrict__ out) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= F) return;
-  double acc[NSTAT] = {0, 0, DBL_MAX, -DBL_MAX, 0, 0, 0, 0, 0};
+  double acc[NSTAT] = {0, 0, INFINITY, -INFINITY, 0, 0, 0, 0, 0};
   for (int k = 0; k < chunks; ++k) {
     const double* p = part + ((int64_t)f * chunks + k) * NSTAT;
-    acc[0] += p[0]; acc[1] += p[1]; acc[2] = fmin(acc[2], p[2]); acc[3] = fmax(acc[3], p[3]);
+    acc[0] += p[0]; acc[1] += p[1]; acc[2] = nan_min(acc[2], p[2]); acc[3] = nan_max(acc[3], p[3]);
     for (int s = 4; s < NSTAT; ++s) acc[s] += p[s];
   }
   for (int s = 0; s < NSTAT; ++s) out[(int64_t)f * NSTAT + s] = acc[s];
@@ -114,7 +127,7 @@ __global__ void __launch_bounds__(256) rff_hist_kernel(const void* const* __rest
   for (int i = threadIdx.x; i < nb; i += blockDim.x) lh[i] = 0u;
   __syncthreads();
   const double step = degenerate ? 1.0 : (mx - mn) / (bins - 2.0);
-  const double top = mn + step * (bins - 1);
+  const double top = split_at(mn, step, bins - 1);
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk;
   const int64_t r1 = min(n, r0 + rows_per_chunk);
   const void* v = vals[f];
@@ -130,8 +143,8 @@ __global__ void __launch_bounds__(256) rff_hist_kernel(const void* const* __rest
       b = (int)floor((x - mn) / step);
       if (b > bins - 2) b = bins - 2;
       // exact split comparison at bucket edges (splits are min + step * k)
-      if (b > 0 && x < mn + step * b) --b;
-      else if (b < bins - 2 && x >= mn + step * (b + 1)) ++b;
+      if (b > 0 && x < split_at(mn, step, b)) --b;
+      else if (b < bins - 2 && x >= split_at(mn, step, b + 1)) ++b;
     } else {
       b = bins - 1;
     }

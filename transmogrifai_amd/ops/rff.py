@@ -1,8 +1,11 @@
 """Numeric raw-column statistics for the RawFeatureFilter (``csrc/hip/rff_kernels.hip``).
 
 ``numeric_summary`` -> ``[F, 9]`` float64: count, nulls, min, max, sum, sum^2, sum^3, sum^4, and
-sum(label over null rows) (the cross term of the null-indicator / label correlation).
-``numeric_hist`` -> ``[F, bins]`` counts with the reference bucketing (``FeatureDistribution.histValues``).
+sum(label over null rows) (the cross term of the null-indicator / label correlation). A column without valid values
+has min = +inf and max = -inf; a NaN among the valid values propagates into min and max (``math.min`` / ``math.max``).
+``numeric_hist`` -> ``[F, bins]`` counts with the reference bucketing (``FeatureDistribution.histValues``): split ``b`` is
+``min + step * b``, a rounded multiply then a rounded add on both paths (never fused), so a value that sits on a split,
+a column maximum or an integer code, lands in the same bucket everywhere.
 Device columns run on the HIP kernels (pointer arrays, no staging copy); host columns use the torch
 reference below, which is the numerics spec the kernels are tested against.
 """

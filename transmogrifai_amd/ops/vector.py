@@ -204,11 +204,13 @@ def onehot_pivot(out: torch.Tensor, codes: Sequence[torch.Tensor], luts: Sequenc
 
 
 def onehot_scatter(out: torch.Tensor, codes: torch.Tensor, lut: torch.Tensor, off: int) -> None:
-    """``out[r, off + lut[codes[r]]] += 1`` (code -1 uses the last lut entry; slot -1 = skip)."""
+    """``out[r, off + lut[codes[r]]] += 1``: a code in ``[0, len(lut) - 1)`` uses its own entry, any other (-1 =
+    missing, other negatives, codes past the dictionary) the last one, as ``onehot_pivot_kernel``; slot -1 = skip."""
     n = codes.shape[0]
     if n == 0:
         return
-    idx = torch.where(codes >= 0, codes.long(), torch.full_like(codes.long(), lut.numel() - 1))
+    last = lut.numel() - 1
+    idx = torch.where((codes >= 0) & (codes < last), codes.long(), torch.full_like(codes.long(), last))
     slot = lut[idx]
     rows = torch.arange(n, device=codes.device)
     m = slot >= 0
