@@ -159,6 +159,13 @@ class Learner:
         raise NotImplementedError(f"{self.name} has no exact partial dependence; it is built on the bin grid of the "
                                   "tree learners")
 
+    def partial_dependence_pairs(self, state, X: torch.Tensor, pairs, rows=None, context=None, scale: str = "raw"):
+        """Exact two-way partial dependence of the model's score on each pair of columns over the model's own bin
+        grid (tree learners: rectangles below the tree paths): ``(values [Pn, NB, NB, C'], valid [Pn, NB, NB],
+        counts [Pn, NB, NB])``."""
+        raise NotImplementedError(f"{self.name} has no exact partial dependence; it is built on the bin grid of the "
+                                  "tree learners")
+
     def state_to_json(self, state: dict) -> dict:
         from ..utils.serde import encode
         return encode(state)

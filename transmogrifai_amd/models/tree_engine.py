@@ -1792,3 +1792,74 @@ def forest_partial_dependence(forest: Forest, Xb: torch.Tensor, cols, n_grid: in
         lp.tree_out.ctypes.data, lp.missing_bin, C, scale, 0 if ice else 1, N.ptr(out),
         None if _walks is None else _walks.ctypes.data), "forest_pd_cpu")
     return out
+
+
+# ------------------------------------------------------------------------------- two-way partial dependence surfaces
+def forest_partial_dependence_pairs(forest: Forest, Xb: torch.Tensor, pairs, n_grid: int,
+                                    rows: Optional[torch.Tensor] = None, tree_weight: Optional[np.ndarray] = None,
+                                    tree_out: Optional[np.ndarray] = None, n_out: Optional[int] = None,
+                                    plan: Optional[ForestLoco] = None, ice: bool = False,
+                                    _walks: Optional[np.ndarray] = None) -> torch.Tensor:
+    """Exact two-way partial dependence of the forest's ``tree_weight``-weighted leaf-value sum on rows ``rows``
+    (None = all) of the binned matrix, over the complete bin grid of the column pairs ``pairs`` (int ``[Pn, 2]``
+    matrix columns, the two of a pair different; columns no tree splits on are allowed, and the same pair may occur
+    again, in either order): float64 ``sum2 [Pn, NB, NB, C]`` on the matrix's device, ``sum2[p, i, j] = sum_r s(x_r
+    with column pairs[p, 0] replaced by bin i and column pairs[p, 1] by bin j)``. ``NB``, ``tree_out`` / ``n_out`` /
+    ``tree_weight`` / ``rows`` / ``plan`` are those of :func:`forest_partial_dependence`. With ``ice=True`` the
+    per-record surfaces ``ice2 [n, Pn, NB, NB, C]`` instead (``n * Pn * NB^2 * C * 8`` bytes: callers that only
+    reduce them pass their rows in blocks).
+
+    Device matrices run ``tmog_hip_forest_pd_pairs``; host matrices, and a launch whose one row x one grid line is
+    beyond the LDS limit, run the host twin -- both sum the same int64 fixed-point integers, so they agree bit for
+    bit. ``_walks`` (host matrices only): an int64 ``[3]`` array that the host twin adds its counts of base walks,
+    anchor searches and rectangle walks to (``benchmarks/bench_partial_dependence_pairs.py``)."""
+    lp = plan if plan is not None else forest_loco_plan(forest, tree_weight, tree_out)
+    if Xb.dtype != torch.uint8 or Xb.dim() != 2:
+        raise ValueError("Xb must be a uint8 [N, F] matrix")
+    dev = Xb.device
+    Xb, Nrows, F, C, row_list, n, used64 = _explain_rows(lp, Xb, rows, n_out)
+    NB = int(n_grid)
+    if not 1 <= NB <= 256:
+        raise ValueError(f"n_grid = {NB}: the grid is the model's histogram width, 1 .. 256")
+    if 0 <= lp.missing_bin < NB - 1:
+        raise ValueError(f"the missing bin {lp.missing_bin} must be the last point of the grid of {NB}")
+    pq = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, np.int64)
+    if pq.size == 0:
+        pq = pq.reshape(0, 2)
+    if pq.ndim != 2 or pq.shape[1] != 2:
+        raise ValueError("pairs must be an int [Pn, 2] array of matrix columns")
+    Pn = int(pq.shape[0])
+    if Pn and (int(pq.min()) < 0 or int(pq.max()) >= F):
+        raise ValueError("pairs names a column outside the matrix")
+    if (pq[:, 0] == pq[:, 1]).any():
+        raise ValueError("the two columns of a pair must be different")
+    slot_of = np.full(F, -1, np.int32)
+    slot_of[lp.used] = np.arange(lp.used.size, dtype=np.int32)
+    pair_slots = np.ascontiguousarray(slot_of[pq], np.int32)
+    if row_list is not None and n and not (0 <= int(row_list.min()) and int(row_list.max()) < Nrows):
+        raise ValueError("rows names a row outside the matrix")
+    U, T, KV = int(lp.used.size), int(lp.tree_weight.size), int(lp.value.shape[1])
+    # the sum of n rows at a scale smaller by 2^ceil(log2 n): the same bound as one row's surface
+    scale = lp.scale if ice else lp.scale / 2.0 ** max(0, (n - 1).bit_length())
+    shape = (n, Pn, NB, NB, C) if ice else (Pn, NB, NB, C)
+    if dev.type == "cuda":
+        d = lp.on(dev)
+        slot_d = _const_tensor(pair_slots.reshape(-1), dev)
+        out = torch.empty(shape, dtype=torch.float64, device=dev) if ice else \
+            torch.zeros(shape, dtype=torch.int64, device=dev)
+        rc = N.hip().tmog_hip_forest_pd_pairs(
+            N.ptr(Xb), F, n, N.ptr(row_list), U, N.ptr(d[0]), N.ptr(slot_d), Pn, NB, T, N.ptr(d[1]), N.ptr(d[2]),
+            int(lp.nodes.shape[0]), N.ptr(d[3]), KV, N.ptr(d[4]), N.ptr(d[5]), lp.missing_bin, C, scale,
+            0 if ice else 1, N.ptr(out), N.stream(dev))
+        if rc == -3:                 # one row x one grid line beyond the LDS limit
+            return _on_host_twin(Xb, row_list, lambda sub: forest_partial_dependence_pairs(
+                forest, sub, pq, NB, None, n_out=C, plan=lp, ice=ice))
+        N.check(rc, "forest_pd_pairs")
+        return out if ice else out.to(torch.float64) * (1.0 / scale)
+    out = torch.empty(shape, dtype=torch.float64)
+    N.check(N.host().tmog_forest_pd_pairs_cpu(
+        N.ptr(Xb), F, n, N.ptr(row_list), U, lp.used.ctypes.data, pair_slots.ctypes.data, Pn, NB, T,
+        lp.tree_off.ctypes.data, lp.nodes.ctypes.data, lp.value.ctypes.data, KV, lp.tree_weight.ctypes.data,
+        lp.tree_out.ctypes.data, lp.missing_bin, C, scale, 0 if ice else 1, N.ptr(out),
+        None if _walks is None else _walks.ctypes.data), "forest_pd_pairs_cpu")
+    return out

@@ -139,8 +139,8 @@ def _loco_outputs(outputs, out: torch.Tensor, base_margin: float):
 PD_ICE_BLOCK_BYTES = 256 << 20      # the ICE curves of one row block of the response scale
 
 
-def _partial_dependence(forest, spec: BinSpec, Xb: torch.Tensor, plan, columns, rows, n_out: int, raw_of, scores,
-                        scale: str, ice: bool):
+def _partial_dependence(forest, spec: BinSpec, Xb: torch.Tensor, plan, n_out: int, raw_of, scores, scale: str,
+                        ice: bool, columns, rows):
     """``partial_dependence`` of the tree learners over ``TE.forest_partial_dependence``. ``raw_of(sums [..., C])``
     maps the additive sums to the columns ``shap_values`` attributes (linear: applied to the mean),
     ``scores(sums [k, C]) -> [k, C']`` to the probabilities / the prediction (applied per curve point, in row
@@ -183,6 +183,46 @@ def _partial_dependence(forest, spec: BinSpec, Xb: torch.Tensor, plan, columns, 
         if ice:
             curves = torch.cat(kept, 0)
     return values, valid, counts, curves
+
+
+def _partial_dependence_pairs(forest, spec: BinSpec, Xb: torch.Tensor, plan, n_out: int, raw_of, scores, scale: str,
+                              pairs, rows):
+    """``partial_dependence_pairs`` of the tree learners over ``TE.forest_partial_dependence_pairs``, with the
+    ``raw_of`` / ``scores`` of :func:`_partial_dependence`: ``(values [Pn, NB, NB, C'], valid [Pn, NB, NB],
+    counts [Pn, NB, NB])``. ``valid`` is the outer product of the two columns' valid bins, ``counts`` the 2-D
+    histogram of the rows' own bins."""
+    if scale not in ("raw", "response"):
+        raise ValueError(f"scale must be 'raw' or 'response', got {scale!r}")
+    dev = Xb.device
+    pq = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, np.int64).reshape(-1, 2)
+    Pn, NB, F = int(pq.shape[0]), int(spec.B), int(Xb.shape[1])
+    if Pn and (int(pq.min()) < 0 or int(pq.max()) >= F):
+        raise ValueError("pairs names a column outside the feature vector")
+    rows = None if rows is None else torch.as_tensor(rows).to(dev).to(torch.long).reshape(-1)
+    n = int(Xb.shape[0]) if rows is None else int(rows.numel())
+    if n == 0:
+        raise ValueError("partial dependence needs at least one row")
+    sel = (Xb if rows is None else Xb.index_select(0, rows)).index_select(
+        1, torch.as_tensor(pq.reshape(-1), device=dev)).to(torch.long).clamp_max(NB - 1).reshape(n, Pn, 2)
+    cell = (torch.arange(Pn, device=dev) * NB + sel[:, :, 0]) * NB + sel[:, :, 1]
+    counts = torch.bincount(cell.reshape(-1), minlength=Pn * NB * NB).reshape(Pn, NB, NB)
+    b = torch.arange(NB, device=dev)
+    ok = b[None, None, :] < torch.as_tensor(spec.n_bins[pq].astype(np.int64), device=dev)[:, :, None]
+    if spec.missing_bin >= 0:
+        ok = ok | (b == int(spec.missing_bin))
+    valid = ok[:, 0, :, None] & ok[:, 1, None, :]
+    if scale == "raw":
+        values = raw_of(TE.forest_partial_dependence_pairs(forest, Xb, pq, NB, rows, n_out=n_out, plan=plan) / n)
+    else:
+        block = max(1, PD_ICE_BLOCK_BYTES // max(1, Pn * NB * NB * n_out * 8))
+        total = None
+        for a in range(0, n, block):
+            r = torch.arange(a, min(n, a + block), device=dev) if rows is None else rows[a:a + block]
+            c = TE.forest_partial_dependence_pairs(forest, Xb, pq, NB, r, n_out=n_out, plan=plan, ice=True)
+            c = scores(c.reshape(-1, n_out)).reshape(c.shape[0], Pn, NB, NB, -1).sum(0)
+            total = c if total is None else total + c
+        values = total / n
+    return values, valid, counts
 
 
 def _subset_size(strategy, F: int, classification: bool, num_trees: int) -> int:
@@ -480,13 +520,24 @@ class _ForestLearner(Learner):
         the kernel; ``scale="response"``: the mean of the probabilities (a regressor: the prediction), every ICE
         curve pushed through ``_outputs`` in row blocks. ``valid`` marks the bins the column has (and the missing
         bin), ``counts`` how many of the rows sit in each bin; ``ice=True`` also returns the per-record curves."""
+        return _partial_dependence(*self._pd_parts(state, X, context), scale, ice, columns, rows)
+
+    def partial_dependence_pairs(self, state, X, pairs, rows=None, context=None, scale="raw"):
+        """Exact two-way partial dependence of the score on each pair of ``pairs`` (int ``[Pn, 2]`` columns of the
+        feature vector) over the model's complete bin grid (``TE.forest_partial_dependence_pairs``): ``(values
+        float64 [Pn, NB, NB, C'], valid bool [Pn, NB, NB], counts int64 [Pn, NB, NB])`` for rows ``rows`` (None:
+        all), the scales of :meth:`partial_dependence`. ``valid`` marks the cells whose two bins the columns have,
+        ``counts`` how many of the rows sit in each cell."""
+        return _partial_dependence_pairs(*self._pd_parts(state, X, context), scale, pairs, rows)
+
+    def _pd_parts(self, state, X, context):
+        """What both partial dependence methods hand on: ``(forest, spec, Xb, plan, n_out, raw_of, scores)``."""
         forest, Xb = self._binned(state, X, context)
         if "_loco_plan" not in state:
             state["_loco_plan"] = TE.forest_loco_plan(forest)
         div = max(1, int(state.get("num_trees", 1))) if (not self.classification and self.is_forest) else 1
-        return _partial_dependence(forest, self._forest(state)[1], Xb, state["_loco_plan"], columns, rows,
-                                   state["_loco_plan"].n_out, lambda s: s / div if div != 1 else s,
-                                   lambda s: _score_columns(self._outputs(state, s)), scale, ice)
+        return (forest, self._forest(state)[1], Xb, state["_loco_plan"], state["_loco_plan"].n_out,
+                lambda s: s / div if div != 1 else s, lambda s: _score_columns(self._outputs(state, s)))
 
     def predict_batch(self, states, X, rows, context=None):
         if not states:
@@ -840,6 +891,18 @@ class _BoostLearner(Learner):
         the probabilities (a regressor: the prediction), every ICE curve pushed through ``_outputs`` in row blocks.
         ``valid`` marks the bins the column has (and the missing bin), ``counts`` how many of the rows sit in each
         bin; ``ice=True`` also returns the per-record curves."""
+        return _partial_dependence(*self._pd_parts(state, X, context), scale, ice, columns, rows)
+
+    def partial_dependence_pairs(self, state, X, pairs, rows=None, context=None, scale="raw"):
+        """Exact two-way partial dependence of the score on each pair of ``pairs`` (int ``[Pn, 2]`` columns of the
+        feature vector) over the model's complete bin grid (``TE.forest_partial_dependence_pairs``): ``(values
+        float64 [Pn, NB, NB, C'], valid bool [Pn, NB, NB], counts int64 [Pn, NB, NB])`` for rows ``rows`` (None:
+        all), the scales of :meth:`partial_dependence`. ``valid`` marks the cells whose two bins the columns have,
+        ``counts`` how many of the rows sit in each cell."""
+        return _partial_dependence_pairs(*self._pd_parts(state, X, context), scale, pairs, rows)
+
+    def _pd_parts(self, state, X, context):
+        """What both partial dependence methods hand on: ``(forest, spec, Xb, plan, n_out, raw_of, scores)``."""
         forest, Xb = self._binned_for(state, X, context)
         multi = state.get("objective") in MULTI_OBJECTIVES
         K = int(state["n_classes"]) if multi else 1
@@ -853,9 +916,8 @@ class _BoostLearner(Learner):
             m = s + bm
             return torch.cat([-m, m], -1) if binary else m
 
-        return _partial_dependence(forest, self._forest(state)[1], Xb, state["_loco_plan"], columns, rows, K, raw_of,
-                                   lambda s: _score_columns(self._outputs(state, (s + bm) if multi else s[:, 0] + bm)),
-                                   scale, ice)
+        return (forest, self._forest(state)[1], Xb, state["_loco_plan"], K, raw_of,
+                lambda s: _score_columns(self._outputs(state, (s + bm) if multi else s[:, 0] + bm)))
 
     def predict_batch(self, states, X, rows, context=None):
         return [self._outputs(s, self.margin(s, X, r, context)) for s, r in zip(states, rows)]

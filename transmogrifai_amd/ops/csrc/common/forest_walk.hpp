@@ -1,4 +1,5 @@
-// What the forest explanation engines (path-perturbation LOCO, partial dependence / ICE, TreeSHAP) share between
+// What the forest explanation engines (path-perturbation LOCO, partial dependence / ICE and its two-way surfaces
+// -- common/pd_pair_walk.hpp has their rectangle enumeration --, TreeSHAP) share between
 // their HIP kernels and their host twins, written once: the packed node record and the walk over it, the
 // fixed-point contribution, and the decoding of a merged TreeSHAP path element. The kernels and the twins promise
 // the same integers bit for bit; all of them evaluate the functions below, so a rule cannot change on one side only.

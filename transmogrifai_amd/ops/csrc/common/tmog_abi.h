@@ -213,6 +213,22 @@ int tmog_forest_pd_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_l
                        const int32_t* tree_out, int missing_bin, int C, double scale, int mode, double* out,
                        int64_t* walks);
 
+// ---- host/pd_pairs_cpu.cpp
+// Exact two-way partial dependence surfaces over the complete bin grid: for rows row_list[0 .. n) (null: rows
+// 0 .. n-1) of Xb [.][F] and the Pn requested column pairs, ice2[i][p][bi][bj][C] = the forest's weighted leaf-value
+// sum of row i with the pair's first column replaced by bin bi and its second by bin bj, both in [0, NB). The
+// arguments are those of tmog_forest_pd_cpu except pair_slots [Pn][2]: the slots in used[U] of the pair's two
+// columns, -1 for a column no tree splits on; the two slots of a pair differ unless both are -1, pairs may repeat.
+// mode 0: out is ice2, fp64 [n][Pn][NB][NB][C]; mode != 0: out is the sum over the rows, fp64 [Pn][NB][NB][C]. The
+// same int64 fixed point as tmog_forest_pd_cpu (hip/pd_pair_kernels.hip has the rule and the bound). walks (may be
+// null): [0] += base walks, [1] += anchor searches, [2] += the walks of the rectangles below the anchors. Returns
+// -1 for a grid the rule of tmog_forest_pd_cpu excludes.
+int tmog_forest_pd_pairs_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
+                             const int32_t* pair_slots, int Pn, int NB, int64_t T, const int64_t* tree_off,
+                             const int32_t* nodes, const float* value, int KV, const float* tree_weight,
+                             const int32_t* tree_out, int missing_bin, int C, double scale, int mode, double* out,
+                             int64_t* walks);
+
 // ---- host/shap_cpu.cpp: host twins of hip/shap_kernels.hip (same arguments minus the stream), plain fp64 sums
 int tmog_forest_shap_cpu(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
                          int64_t P, const int64_t* p_off, const int32_t* p_out, const double* p_val, int KV,

@@ -1,5 +1,5 @@
-// The scaffold of the forest explanation kernels (shap_kernels.hip, loco_kernels.hip, pd_kernels.hip), written
-// once. A workgroup of kTileThreads lanes owns a tile of rows: it zeroes an int64 fixed-point tile in LDS, stages
+// The scaffold of the forest explanation kernels (shap_kernels.hip, loco_kernels.hip, pd_kernels.hip,
+// pd_pair_kernels.hip), written once. A workgroup of kTileThreads lanes owns a tile of rows: it zeroes an int64 fixed-point tile in LDS, stages
 // the bins of the forest's used columns of its rows next to it, accumulates with 64-bit LDS integer atomics and at
 // the end converts the tile to fp64 and writes it with plain stores. The launchers size the tile from the LDS
 // budget by one rule and start the kernel through one function.

@@ -115,6 +115,13 @@ int tmog_hip_forest_pd(const uint8_t* Xb, int F, int64_t n, const int32_t* row_l
                        const int32_t* tree_out, int missing_bin, int C, double scale, int mode, void* out,
                        hipStream_t stream);
 
+// ---- hip/pd_pair_kernels.hip
+int tmog_hip_forest_pd_pairs(const uint8_t* Xb, int F, int64_t n, const int32_t* row_list, int U, const int32_t* used,
+                             const int32_t* pair_slots, int Pn, int NB, int64_t T, const int64_t* tree_off,
+                             const int32_t* nodes, int64_t n_nodes, const float* value, int KV,
+                             const float* tree_weight, const int32_t* tree_out, int missing_bin, int C, double scale,
+                             int mode, void* out, hipStream_t stream);
+
 // ---- hip/rff_kernels.hip
 int tmog_hip_rff_summary(const void* const* vals, const uint8_t* const* valid, const int32_t* dtype, int64_t n, int F,
                          const void* label, int label_dt, double* out, hipStream_t stream);

@@ -565,6 +565,14 @@ class OpWorkflowModel(OpWorkflowCore):
         from ..insights.partial_dependence import partial_dependence
         return partial_dependence(self, data, features, top_k, scale, sample, seed, ice, feature)
 
+    def partial_dependence_pairs(self, data=None, pairs=None, top_k: int = 4, scale: str = "response",
+                                 sample: Optional[int] = 10_000, seed: int = 0,
+                                 feature: Optional[FeatureLike] = None):
+        """Exact two-way partial dependence surfaces of the selected tree model over its bin grid, with Friedman's
+        H-statistic per pair (``insights.partial_dependence.partial_dependence_pairs`` has the arguments)."""
+        from ..insights.partial_dependence import partial_dependence_pairs
+        return partial_dependence_pairs(self, data, pairs, top_k, scale, sample, seed, feature)
+
     def summary_json(self) -> Dict:
         from ..selector.model_selector import ModelSelector
         out = {}
