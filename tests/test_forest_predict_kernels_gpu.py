@@ -1,4 +1,4 @@
-"""Kernel-level oracle tests of the forest scoring kernels in ``ops/csrc/hip/tree_kernels.hip``:
+"""Kernel-level oracle tests of the forest scoring kernels in ``ops/csrc/hip/forest_predict_kernels.hip``:
 ``forest_predict_lds_kernel<NS>`` (F <= 512), ``forest_predict_kernel<NS>`` (the F > 512 fallback) and
 ``forest_predict_multi_kernel<NS, 1|2|4|8, VKP>``, each over both node sources ``NS`` (``ImageNodes``, the packed node
 image, and ``DirectNodes``, which ``TMOG_PREDICT_V1=1`` selects: the autouse fixture ``node_source`` patches

@@ -1,4 +1,4 @@
-"""The scoring kernels of ``ops/csrc/hip/tree_kernels.hip`` (``forest_predict_lds_kernel``, ``forest_predict_kernel``
+"""The kernels of ``ops/csrc/hip/forest_predict_kernels.hip`` (``forest_predict_lds_kernel``, ``forest_predict_kernel``
 and ``forest_predict_multi_kernel<NS, KT, VKP>``) over the packed node image that ``forest_image_kernel`` builds,
 against
 

@@ -219,7 +219,7 @@ def test_native_finalize_matches_numpy(mode, monkeypatch):
 
 def _grow_wide(dev, F=136, n_one=12, N=20_000, chunk_rows=4096):
     """XGBoost-style Newton trees on a dword-aligned matrix (F % 4 == 0): on the GPU the multi-bin groups
-    run the wide-load histogram items (tree_kernels.hip hist_wide_item), groups sized in multiples of 4."""
+    run the wide-load histogram items (tree_hist_kernels.hip hist_wide_item), groups sized in multiples of 4."""
     g = torch.Generator().manual_seed(11)
     B = 32
     X = torch.randint(0, B - 1, (N, F), generator=g, dtype=torch.uint8)

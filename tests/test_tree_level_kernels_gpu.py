@@ -1,6 +1,6 @@
-"""Kernel-level oracle tests of the per-level tree kernels in ``ops/csrc/hip/tree_kernels.hip``: ``hist_build_kernel``
-(byte gather, register accumulation, CSR and wide-load items), ``hist_subtract_kernel``, ``zero_segments_kernel``,
-``partition_fused_kernel`` and ``leaf_collect_kernel``, each driven through its C entry point with ctypes on crafted
+"""Kernel-level oracle tests of the per-level tree kernels: ``hist_build_kernel`` (byte gather, register accumulation,
+CSR and wide-load items), ``hist_subtract_kernel`` and ``zero_segments_kernel`` of ``ops/csrc/hip/tree_hist_kernels.hip``,
+``partition_fused_kernel`` and ``leaf_collect_kernel`` of ``ops/csrc/hip/tree_partition_kernels.hip``, each driven through its C entry point with ctypes on crafted
 inputs and compared with the NumPy oracle of tests/tree_level_oracle.py (validated against the host twins in
 tests/test_tree_level_oracle.py).
 

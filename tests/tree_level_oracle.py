@@ -1,5 +1,5 @@
 """NumPy oracle of the per-level tree kernels (histogram build, subtract, zero, partition, leaf collect), written
-from the layout contract at the top of ``ops/csrc/hip/tree_kernels.hip`` -- not from the kernel bodies:
+from the layout contract at the top of ``ops/csrc/hip/tree_hist_kernels.hip`` -- not from the kernel bodies:
 
   Xb    uint8 [N][F] row-major bins            rows  uint32 entries, ``row | weight << 24`` (``wide``: the row id,
                                                      weight 1)

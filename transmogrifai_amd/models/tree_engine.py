@@ -40,7 +40,7 @@ MAX_WIDE_ROWS = 1 << 31       # wide entries (32-bit row id, weight 1)
 def wide_rows(n_rows: int) -> bool:
     """Entry format of a training set of ``n_rows`` rows: below 2^24 rows the row id and an 8-bit weight share
     one 32-bit entry; from 2^24 rows on (or with ``TMOG_TREE_WIDE_ROWS=1``, for tests) an entry is the row id
-    alone and weights become repeated entries (``tree_kernels.hip`` ``ent_row`` / ``ent_w``)."""
+    alone and weights become repeated entries (``tree_dev.hpp`` ``ent_row`` / ``ent_w``)."""
     return n_rows >= MAX_ROWS or os.environ.get("TMOG_TREE_WIDE_ROWS") == "1"
 
 # Native per-group resource slots (stream, staging, histogram buffers; tree_grow_hip.hip slots()): grower calls
@@ -425,7 +425,7 @@ def _entry_models(models: tuple, counts: tuple, dev) -> torch.Tensor:
 
 def _stage_gh(rows: torch.Tensor, counts, jobs, t1f, t2f, qscale, stride: int, wide: bool = False) -> torch.Tensor:
     """``[total, 2]`` int32: each root entry's quantised (q(w g), q(w h)) under its job's model scales -- the
-    histogram kernels' ``rintf((w * t) * qscale)`` in the same fp32 operation order (tree_kernels.hip
+    histogram kernels' ``rintf((w * t) * qscale)`` in the same fp32 operation order (tree_hist_kernels.hip
     stage_row), so the histograms are bit-identical to gathering t1 / t2 per row."""
     dev = rows.device
     e = rows.to(torch.int64) & 0xFFFFFFFF
@@ -842,7 +842,7 @@ def boost_prologue(root: torch.Tensor, counts, act, G: torch.Tensor, H: torch.Te
 
 def _quant_scales(mode, S, jobs, t1f, t2f, rows, chunk_rows, dev, amax_hint=None, wmax_hint=None):
     """Per-(model, stat) power-of-two fixed-point scales for the int64 histograms (see the
-    "Fixed-point statistics" note in ops/csrc/hip/tree_kernels.hip). A row's contribution is
+    "Fixed-point statistics" note in ops/csrc/hip/tree_hist_kernels.hip). A row's contribution is
     ``rint(v * scale)`` with ``|v * scale| <= qmax``, so a ``chunk_rows``-row LDS partial fits int32.
     Computed on the device (no host sync); returns (float32 scales, float64 inverses), ``[n_models, S]``."""
     n_models = max([j.model for j in jobs], default=0) + 1
@@ -1006,7 +1006,7 @@ def _finalize_py(jobs, G: "_Nodes", mode, kind, K, S, missing_bin, with_gid_valu
     return f
 
 
-_PM_VK = N.ABI_CONSTS["TMOG_PM_VK"]      # tree_kernels.hip forest_predict_multi_kernel: variants x classes per model
+_PM_VK = N.ABI_CONSTS["TMOG_PM_VK"]      # forest_predict_kernels.hip forest_predict_multi_kernel: variants x classes per model
 _PM_DEPTHS = 32                          # ... and its s_dmask: per-depth stop masks for depths 0.._PM_DEPTHS
 
 
@@ -1043,7 +1043,7 @@ def predict_v1() -> bool:
 
 
 def pack_node_image(nodes: np.ndarray, default_left: np.ndarray, mask: Optional[np.ndarray] = None) -> np.ndarray:
-    """uint32 ``[n, 4]``: the record ``forest_image_kernel`` (tree_kernels.hip) packs for every node,
+    """uint32 ``[n, 4]``: the record ``forest_image_kernel`` (forest_predict_kernels.hip) packs for every node,
     ``(feat | bin << 16 | default_left << 24, variant stop mask, left, right)``: its host twin."""
     nd = np.asarray(nodes, np.int32).reshape(-1, 4)
     img = np.zeros((len(nd), 4), np.uint32)

@@ -1074,7 +1074,7 @@ def _xgb_growth_matrix(Xb, spec, dev, par):
             colperm = order.astype(np.int64)
             Xg = Xb.index_select(1, torch.as_tensor(colperm, device=dev)).contiguous()
             n_bins_g = nb_all[colperm]
-    # wide-load histogram items (tree_kernels.hip hist_wide_item) read 4 bins per lane with dword loads:
+    # wide-load histogram items (tree_hist_kernels.hip hist_wide_item) read 4 bins per lane with dword loads:
     # pad the growth matrix to a dword row stride with columns that hold only the missing bin (one
     # "present" bin that no row has: they can never split, and are mapped to column 0 if ever read)
     if dev.type == "cuda" and spec.missing_bin > 0 and os.environ.get("TMOG_HIST_WIDE") != "0" \
@@ -1098,7 +1098,7 @@ def _xgb_growth_matrix(Xb, spec, dev, par):
             Xh = Xg[:, :Fh].contiguous()
     # feature-parallel over the ranks: this rank's slice of the growth-order feature lists
     fp = TE.fp_plan(Xg, n_bins_g, par, sparse=spec.missing_bin >= 0) if par is not None else None
-    # one-hot / null-indicator columns: histogram from the rows' CSR lists (tree_kernels.hip)
+    # one-hot / null-indicator columns: histogram from the rows' CSR lists (tree_hist_kernels.hip)
     csr = TE.onebin_csr(Xg, n_bins_g, cols=None if fp is None else fp.one_cols) \
         if (dev.type == "cuda" and spec.missing_bin > 0) else None
     # feature-major copy for the partition kernel's split-column reads (tmog_abi.h GrowArgs.XbT)

@@ -144,7 +144,7 @@ def build_hip(force: bool = False, arch: str = ARCH) -> Path:
             from concurrent.futures import ThreadPoolExecutor
             srcs = srcs + [_provenance_source("hip", source_hash("hip", arch))]
             objs = [str(LIB / (s.stem + ".o")) for s in srcs]
-            # one hipcc per translation unit, a few at a time (the tree kernels alone take ~1 min)
+            # one hipcc per translation unit, a few at a time (tree_split_kernels.hip takes the longest)
             with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))) as ex:
                 list(ex.map(lambda so: _run([hipcc, f"--offload-arch={arch}"] + HIP_FLAGS +
                                             [f"-I{CSRC}", "-o", so[1], str(so[0])]),

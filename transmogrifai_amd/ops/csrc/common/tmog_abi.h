@@ -40,8 +40,8 @@
 #define TMOG_ITEM_WIDE 16          // wide-load item: contiguous dword-aligned physical columns
 #define TMOG_ITEM_SC_SHIFT 8       // bits 8..15: statistic chunk
 
-// ---- work items of the tree level kernels (hip/tree_kernels.hip), laid out by common/tree_plan.hpp for the host
-// planner (common/tree_grow.hpp) and the device planner (hip/tree_resident.hip)
+// ---- work items of the tree level kernels (hip/tree_hist_kernels.hip, hip/tree_partition_kernels.hip), laid out by
+// common/tree_plan.hpp for the host planner (common/tree_grow.hpp) and the device planner (hip/tree_resident.hip)
 typedef struct FeatGroup {
   int32_t f0, nf;   // local features [f0, f0 + nf) of one histogram item (nf <= 64)
   int32_t flags;    // TMOG_ITEM_REG | TMOG_ITEM_CSR | TMOG_ITEM_WIDE

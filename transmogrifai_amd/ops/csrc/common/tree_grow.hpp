@@ -12,8 +12,8 @@
 // Backends (template parameter BK) provide memory, staging and the kernels:
 //   GPU  (hip/tree_grow_hip.hip)   : pinned staging + hipMemcpyAsync, tmog_hip_* launchers
 //   CPU  (host/tree_grow_cpu.cpp)  : host memory, tmog_*_cpu functions (bit-identical results)
-// Layout contracts are those of hip/tree_kernels.hip (packed rows, int64 fixed-point histograms); how a level's nodes
-// become work items is common/tree_plan.hpp, shared with the device planner (hip/tree_resident.hip).
+// Layout contracts are those of hip/tree_hist_kernels.hip (packed rows, int64 fixed-point histograms); how a level's
+// nodes become work items is common/tree_plan.hpp, shared with the device planner (hip/tree_resident.hip).
 #pragma once
 
 #include <algorithm>
@@ -105,7 +105,7 @@ inline bool env_is(const char* name, char c) {
 }
 inline bool pair_scan_enabled() { return !env_is("TMOG_PAIR_SCAN", '0'); }
 inline bool fused_reduce_enabled() { return !env_is("TMOG_FUSED_REDUCE", '0'); }
-// (the launcher in hip/tree_kernels.hip that acts on this one keeps its own once-per-process read)
+// (the launcher in hip/tree_hist_kernels.hip that acts on this one keeps its own once-per-process read)
 inline bool hist_wide_split() { return env_is("TMOG_HIST_WIDE_SPLIT", '1'); }
 // Newton growth gates a split on the children's hessian sums: (g, h) statistics, second-order gain.
 // TMOG_TREE_HESS_GATE=0: off (A/B and the equality test).
@@ -113,7 +113,7 @@ inline bool hess_gate(const GrowArgs& a) {
   return a.mode == 2 && a.kind == 3 && a.S >= 2 && !env_is("TMOG_TREE_HESS_GATE", '0');
 }
 
-// Merge of the ranks' records of node j (host twin of tree_kernels.hip fp_merge_kernel).
+// Merge of the ranks' records of node j (host twin of tree_split_kernels.hip fp_merge_kernel).
 inline void fp_merge_host(const uint8_t* recv, int R, int m, size_t rb, int S, int32_t* feat, int32_t* bin,
                           float* gain, uint8_t* dl, float* left) {
   for (int j = 0; j < m; ++j) fp_merge_node(recv, R, m, j, (int64_t)rb, S, feat, bin, gain, dl, left);
@@ -149,7 +149,7 @@ struct GrowResult {
   std::string error;
 };
 
-// work items of hip/tree_kernels.hip (common/tmog_abi.h)
+// work items of the level kernels (common/tmog_abi.h)
 using HistItemH = ::HistItem;
 using PartItemH = ::PartItem;
 using LeafItemH = ::LeafItem;
@@ -282,7 +282,7 @@ GroupLayout group_layout(const GrowArgs& a, bool use_subset, bool fp) {
     }
     const int n_one = o1 - o0;
     if (GPU && a.csr_ptr && a.csr_col && n_multi > 0 && n_one > 0 && a.csr_nf == n_one &&
-        2 * n_one + 4 + 64 * 4 <= 64 * (B * S + 1))   // sums + list lengths of the CSR item (tree_kernels.hip)
+        2 * n_one + 4 + 64 * 4 <= 64 * (B * S + 1))   // sums + list lengths of the CSR item (tree_hist_kernels.hip)
       full_groups.push_back(FeatGroup{n_multi, n_one, TMOG_ITEM_CSR});   // one item walks the rows' CSR lists
     else
       for (const FeatGroup& g : equal_groups(n_one))

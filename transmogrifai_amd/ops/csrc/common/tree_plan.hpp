@@ -1,4 +1,4 @@
-// How a level's nodes become work items of the level kernels (hip/tree_kernels.hip), written once for the two level
+// How a level's nodes become work items of the level kernels (hip/tree_*_kernels.hip), written once for the two level
 // planners that promise the same trees bit for bit: the host-planned loop (common/tree_grow.hpp grow_group) and the
 // device-planned one (hip/tree_resident.hip level_plan_kernel). Both evaluate the functions below for the sibling
 // flags, the per-node work counts, every item, the zero segments and the parameter slots, so the layout cannot

@@ -1,5 +1,5 @@
 // The arithmetic and decision rules of the tree engine that have a host and a device twin, written once. The CPU
-// grower (host/tree_cpu.cpp), the host-planned HIP grower (common/tree_grow.hpp + hip/tree_kernels.hip) and the
+// grower (host/tree_cpu.cpp), the host-planned HIP grower (common/tree_grow.hpp + hip/tree_*_kernels.hip) and the
 // device-planned grower (hip/tree_resident.hip) promise the same trees bit for bit: all of them evaluate the functions
 // below, so a rule cannot change on one backend only. Stateless free functions of scalar arguments.
 #pragma once
@@ -58,8 +58,8 @@ TMOG_HD bool better(const SplitCand& a, const SplitCand& b) {
   return a.b < b.b;
 }
 
-// body(s) for every statistic s < S: tree_kernels.hip's TM_FOR_S as a function (the macro stays there for the scans'
-// statement bodies). SM > 0: unrolled to the compile-time bound with a run-time guard, so arrays indexed by s stay in
+// body(s) for every statistic s < S: tree_split_kernels.hip's TM_FOR_S as a function (the macro stays there for the
+// scans' statement bodies). SM > 0: unrolled to the compile-time bound with a run-time guard, so arrays indexed by s stay in
 // registers (a loop to the run-time S indexes them dynamically: scratch memory). SM == 0: the plain run-time loop.
 template <int SM, class Body>
 TMOG_HD void for_stats(int S, Body body) {

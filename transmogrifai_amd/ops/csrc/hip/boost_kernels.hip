@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include "hip/tmog_hip_abi.h"
+#include "hip/tree_dev.hpp"
 
 namespace {
 
@@ -58,7 +59,7 @@ __global__ void __launch_bounds__(256) boost_epilogue_kernel(
   int64_t r = 0, t = 0, p = 0;
   int32_t g_id = 0;
   if (ok) {
-    r = wide ? (int64_t)entries[e] : (int64_t)(entries[e] & 0xFFFFFFu);   // tree_kernels.hip ent_row
+    r = (int64_t)tmog::ent_row(entries[e], wide);
     g_id = gid[e];
     ok = g_id >= 0 && g_id < n_gid && r < N;   // defensive: never index out of range
   }

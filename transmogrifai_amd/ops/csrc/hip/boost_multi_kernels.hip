@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "hip/tmog_hip_abi.h"
+#include "hip/tree_dev.hpp"
 
 namespace {
 
@@ -47,7 +48,7 @@ __global__ void __launch_bounds__(256) boost_margin_add_kernel(
     int64_t N, double* __restrict__ F, int64_t n_gid, int64_t n_trees, int64_t Q, int wide) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_entries) return;
-  const int64_t r = wide ? (int64_t)entries[e] : (int64_t)(entries[e] & 0xFFFFFFu);   // tree_kernels.hip ent_row
+  const int64_t r = (int64_t)tmog::ent_row(entries[e], wide);
   const int32_t g_id = gid[e];
   if (g_id < 0 || g_id >= n_gid || r >= N) return;   // defensive: never index out of range
   const int64_t t = gid_tree[g_id];

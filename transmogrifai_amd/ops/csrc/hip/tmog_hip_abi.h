@@ -198,10 +198,12 @@ void* tmog_hip_rccl_comm_init(const char* id_bytes, int world, int rank);
 int tmog_hip_fp_allgather(const void* send, void* recv, int64_t bytes, void* comm, int world, hipStream_t stream);
 int tmog_hip_rccl_comm_destroy(void* comm);
 
-// ---- hip/tree_kernels.hip: the tree level kernels. `items` are HistItem / PartItem / LeafItem arrays on the device.
+// ---- The tree level kernels, four translation units. `items` are HistItem / PartItem / LeafItem arrays on the device.
 // The trailing `const int*` of a launcher (dcount, dm, dnp, dn) is null for host-planned levels; for device-planned
 // levels (tree_resident.hip) it points at the item / node / pair / segment count on the device and the count passed by
 // value is an upper bound that sizes the grid.
+
+// ---- hip/tree_hist_kernels.hip: histograms; tmog_hip_tree_prime loads the code objects of all four units
 int tmog_hip_debug_flags(int flags);
 int tmog_hip_hist_build(const uint8_t* Xb, int F, const uint32_t* rows, const void* items, int n_items,
                         const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* node_model,
@@ -213,6 +215,12 @@ int tmog_hip_hist_build(const uint8_t* Xb, int F, const uint32_t* rows, const vo
 int tmog_hip_hist_subtract(int64_t* hist, const int64_t* parent, const int64_t* parent_off, const int64_t* small_off,
                            const int64_t* out_off, const int64_t* size, int n, int64_t max_size, int64_t dense,
                            int per, int S, hipStream_t stream);
+int tmog_hip_zero_segments(int64_t* hist, const int64_t* off, const int64_t* size, int n, int64_t max_size,
+                           int64_t dense, int per, int S, hipStream_t stream, int n_dense, const int* dn);
+int tmog_hip_tree_prime();
+int tmog_hip_hist_stat_chunk(int B, int S);
+
+// ---- hip/tree_split_kernels.hip: split finding
 int tmog_hip_split_find(const int64_t* hist, int n_nodes, const int64_t* node_hist_off, const int32_t* node_nfeat,
                         const int32_t* node_feat_off, const int32_t* feat_list, const int32_t* feat_nbins, int B,
                         int S, int kind, const float* node_params, int missing_bin, const int32_t* node_model,
@@ -231,11 +239,9 @@ int tmog_hip_fp_merge(const void* recv, int R, int m, int64_t rec_bytes, int S, 
 int tmog_hip_fp_merge_dev(const void* recv, int R, int m_stride, int64_t rec_bytes, int S, int32_t* out_feat,
                           int32_t* out_bin, float* out_gain, uint8_t* out_dl, float* out_left, const int* dm,
                           hipStream_t stream);
-int tmog_hip_zero_segments(int64_t* hist, const int64_t* off, const int64_t* size, int n, int64_t max_size,
-                           int64_t dense, int per, int S, hipStream_t stream, int n_dense, const int* dn);
-int tmog_hip_tree_prime();
 size_t tmog_hip_split_cand_bytes(int n_nodes, int max_nfeat, int B, int S);
-int tmog_hip_hist_stat_chunk(int B, int S);
+
+// ---- hip/tree_partition_kernels.hip: row partition and leaf collection
 int tmog_hip_partition_fused(const uint8_t* Xb, int F, const uint32_t* rows_in, uint32_t* rows_out, const void* items,
                              int n_items, const int64_t* node_begin, const int64_t* node_count,
                              const int32_t* split_feat, const int32_t* split_bin, const uint8_t* dl,
@@ -244,6 +250,8 @@ int tmog_hip_partition_fused(const uint8_t* Xb, int F, const uint32_t* rows_in, 
                              const int* dcount, int wide_rows);
 int tmog_hip_leaf_collect(const uint32_t* rows, const void* items, int n_items, uint32_t* out_rows, int32_t* out_gid,
                           hipStream_t stream, const uint32_t* rows_alt, const int* dcount);
+
+// ---- hip/forest_predict_kernels.hip: forest scoring over the growers' node arrays
 int tmog_hip_forest_predict_multi(const uint8_t* Xb, int F, int n_models, const int64_t* model_row_off,
                                   const int32_t* row_list, int64_t max_rows, const int64_t* model_tree_off,
                                   const int64_t* tree_off, const float* tree_weight, const int32_t* nodes,

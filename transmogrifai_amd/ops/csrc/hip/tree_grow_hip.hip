@@ -1,7 +1,7 @@
 // HIP backend of the native tree grower (common/tree_grow.hpp): one host thread + one HIP stream per
 // job group, pinned staging buffers (three rotating slots per group) with hipMemcpyAsync, grow-only
 // device buffers kept across calls (stream-ordered hipMallocAsync when they grow), and the tmog_hip_* kernel launchers of
-// tree_kernels.hip. The only host<->device synchronisation is one result read per level and group.
+// tree_*_kernels.hip. The only host<->device synchronisation is one result read per level and group.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 

@@ -6,7 +6,7 @@
 // group, 66-170 us of stream idle per level on the XGBoost headline (profiles/r4_levels_base.txt). Here the
 // same plan is computed ON THE DEVICE by one 1024-thread workgroup (level_plan_kernel) between the level
 // kernels, and every level kernel is launched with a host upper bound of its grid and reads the real item
-// count from device memory (tree_kernels.hip `dcount` arguments): the host enqueues a whole tree -- every
+// count from device memory (the `dcount` arguments of tree_*_kernels.hip): the host enqueues a whole tree -- every
 // level, the leaf collection and the tree finalisation (leaf values, gamma pruning; tree_finalize_kernel) --
 // without a single synchronisation, and boosting (models/trees.py) enqueues round after round. The host
 // reads the created-node records once per fit.

@@ -1,7 +1,7 @@
 // CPU reference implementation of the histogram tree engine kernels.
 //
-// These are the host twins of the HIP kernels in ../hip/tree_kernels.hip and share their
-// data layout exactly (see transmogrifai_amd/models/tree_engine.py for the orchestration):
+// These are the host twins of the HIP kernels in ../hip/tree_*_kernels.hip and ../hip/forest_predict_kernels.hip and
+// share their data layout exactly (see transmogrifai_amd/models/tree_engine.py for the orchestration):
 //
 //   Xb        uint8 [N][F] row-major binned feature matrix
 //   rows      uint32 packed row entries: (row & 0xFFFFFF) | (weight << 24); with wide = 1 (training sets of
