@@ -55,6 +55,17 @@ int tmog_hip_xtd(const float* A, int64_t lda, int64_t a_pstride, const float* D,
                  int dg, int64_t d_gstride, int64_t N, int K, int M, int P, int S, float* part, double* out,
                  hipStream_t stream);
 
+// ---- hip/lda_kernels.hip: documents as CSR (int32 columns sorted per row, fp32 counts), expEbT [V][K] fp64.
+// tmog_hip_lda_lds_terms is the number of terms of one document that iterate out of LDS (0 for an unsupported K);
+// queue is one word of scratch for the document queue; partial holds n_seg x K doubles
+int tmog_hip_lda_lds_terms(int K);
+int tmog_hip_lda_estep(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t N, const double* expEbT,
+                       int K, const double* alpha, int iters, double tol, uint32_t* queue, double* gamma,
+                       int32_t* n_iter, double* expEt, double* r, hipStream_t stream);
+int tmog_hip_lda_sstats(const int64_t* seg_begin, const int32_t* csc_row, const int64_t* csc_pos, int64_t n_seg,
+                        const int64_t* col_seg, int64_t V, const double* expEt, const double* r, const double* expEbT,
+                        int K, double* partial, double* sstats, hipStream_t stream);
+
 // ---- hip/linear_bf16_kernels.hip
 int tmog_hip_lr_bf16_blocks_per_cu(int dpad, int grad);
 int tmog_hip_lr_bf16(const void* Xr, int64_t ldr, int64_t N, int dpad, const float* y, const float* W, int ldw,

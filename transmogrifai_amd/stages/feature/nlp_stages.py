@@ -6,7 +6,8 @@ Reference (``core/.../stages/impl/feature/``): ``OpStopWordsRemover.scala``, ``O
 dictionaries), ``MimeTypeDetector.scala`` (Tika) and ``PhoneNumberParser.scala`` (libphonenumber).
 
 Word2Vec (skip-gram with negative sampling) and LDA (batch variational Bayes) are trained with
-dense tensor ops on the engine device (embedding gathers + batched GEMMs). The JVM NLP libraries and
+dense tensor ops on the engine device (embedding gathers + batched GEMMs); LDA on a wide, mostly zero device
+matrix runs its E-step over the non-zeros instead (``ops/lda.py``, HIP). The JVM NLP libraries and
 their model binaries / dictionaries are not available (the reference mount also lacks the large
 blobs, ``.MISSING_LARGE_BLOBS``); the detectors here are compact, documented replacements whose exact
 outputs are "parity unpinned".
@@ -25,6 +26,7 @@ from ...config import vector_dtype
 from ...data.columns import NumericColumn, ObjectColumn, TextColumn, VectorColumn, column_from_values
 from ...data.vector_metadata import OpVectorColumnMetadata, OpVectorMetadata
 from ...features import types as T
+from ...ops import lda as LDA
 from ...utils import text as TU
 from ..base import UnaryEstimator, UnaryTransformer, register_stage
 from .text_stages import detect_mime, is_valid_phone
@@ -241,6 +243,10 @@ class OpLDAModel(VectorizerMixin, UnaryTransformer):
 
     def _infer(self, X: torch.Tensor) -> torch.Tensor:
         lam = torch.as_tensor(self.topics, dtype=torch.float64, device=X.device)
+        if LDA.worthwhile(X, lam.shape[0]):         # sparse E-step kernel (ops/csrc/hip/lda_kernels.hip)
+            return LDA.e_step(LDA.DocTermCSR(X), torch.log(lam.clamp_min(1e-100)),
+                              torch.as_tensor(self.alpha, dtype=torch.float64, device=X.device), self.doc_iter,
+                              sstats=False)[0]
         return lda_e_step(X.to(torch.float64), torch.log(lam.clamp_min(1e-100)),
                           torch.as_tensor(self.alpha, dtype=torch.float64, device=X.device), self.doc_iter)[0]
 
@@ -303,16 +309,22 @@ class OpLDA(VectorizerMixin, UnaryEstimator):
 
     def fit_columns(self, c, ds=None):
         p = self.params
-        X = c.values.to(torch.float64)
-        N, V = X.shape
         K = int(p["k"])
+        # a wide, mostly zero corpus on the device runs the sparse E-step kernel over a CSR built once
+        # (ops/csrc/hip/lda_kernels.hip); everything else the dense fp64 E-step below
+        csr = LDA.DocTermCSR(c.values) if LDA.worthwhile(c.values, K) else None
+        X = c.values.to(torch.float64) if csr is None else c.values
+        N, V = X.shape
         alpha = torch.full((K,), float(p["doc_concentration"] or 1.0 / K), dtype=torch.float64, device=X.device)
         eta = float(p["topic_concentration"] or 1.0 / K)
         g = torch.Generator(device="cpu").manual_seed(int(p["seed"]))
         lam = (torch.rand(K, V, generator=g, dtype=torch.float64) * 0.5 + 0.75).to(X.device)
         for _ in range(int(p["max_iter"])):
             Elogbeta = torch.digamma(lam) - torch.digamma(lam.sum(1, keepdim=True))
-            _, sstats = lda_e_step(X, Elogbeta, alpha, 50)
+            if csr is not None:
+                sstats = LDA.e_step(csr, Elogbeta, alpha, 50)[1]
+            else:
+                _, sstats = lda_e_step(X, Elogbeta, alpha, 50)
             lam = eta + sstats
         topics = lam / lam.sum(1, keepdim=True)
         return OpLDAModel(topics.cpu().numpy(), alpha.cpu().numpy())
