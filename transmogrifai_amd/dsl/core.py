@@ -611,10 +611,11 @@ def _count_vec(self, vocab_size: int = 1 << 18, min_df: float = 1.0, min_tf: flo
 
 @register(T.TextList, "word2vec")
 def _word2vec(self, vector_size: int = 100, window_size: int = 5, min_count: int = 5, max_iter: int = 1,
-              step_size: float = 0.025, **kw):
+              step_size: float = 0.025, trainer: str = "auto", **kw):
+    """``trainer``: ``"pairs"``, ``"windows"`` (HIP, ``ops/word2vec.py``) or ``"auto"``."""
     from ..stages.feature.nlp_stages import OpWord2Vec
     return OpWord2Vec(vector_size=vector_size, window_size=window_size, min_count=min_count, max_iter=max_iter,
-                      step_size=step_size, **kw).set_input(self).get_output()
+                      step_size=step_size, trainer=trainer, **kw).set_input(self).get_output()
 
 
 @register(T.OPVector, "lda")

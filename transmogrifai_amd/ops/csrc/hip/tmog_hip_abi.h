@@ -66,6 +66,22 @@ int tmog_hip_lda_sstats(const int64_t* seg_begin, const int32_t* csc_row, const 
                         const int64_t* col_seg, int64_t V, const double* expEt, const double* r, const double* expEbT,
                         int K, double* partial, double* sstats, hipStream_t stream);
 
+// ---- hip/w2v_kernels.hip: tables [V][Dp] fp32 (Dp a multiple of 16, at most 256), the corpus as token ids with
+// doc_ptr [N + 1] / doc_id [T]; slabs gin, gout [B][16][Dp] with keys [B][16] (V: no row). n_pos is one word on the
+// device (the valid context slots of the batch), lr the SGD rate: a_pos = lr / n_pos, a_neg = a_pos / S.
+// tmog_hip_w2v_apply takes the keys sorted (stable) with order[i] the slab row of sorted position i;
+// tmog_hip_w2v_seg_cap is the number of slab rows summed before a run of equal keys is cut; partial holds
+// 2 * ceil(M / cap) * Dp floats and tail ceil(M / cap) words of scratch
+int tmog_hip_w2v_seg_cap();
+int tmog_hip_w2v_window(const float* emb_in, const float* emb_out, int V, int Dp, const int32_t* tok, int64_t T,
+                        const int64_t* doc_ptr, const int32_t* doc_id, const int32_t* pos, const int32_t* neg, int B,
+                        int w, int S, const int32_t* n_pos, float lr, float* gin, float* gout, int32_t* key_in,
+                        int32_t* key_out, hipStream_t stream);
+int tmog_hip_w2v_apply(float* emb, int V, int Dp, const float* slab, const int32_t* skey, const int64_t* order,
+                       int64_t M, float* partial, int32_t* tail, hipStream_t stream);
+int tmog_hip_w2v_doc_mean(const float* vec, int V, int D, const int32_t* tok, const int64_t* doc_ptr, int64_t N,
+                          float* out, hipStream_t stream);
+
 // ---- hip/linear_bf16_kernels.hip
 int tmog_hip_lr_bf16_blocks_per_cu(int dpad, int grad);
 int tmog_hip_lr_bf16(const void* Xr, int64_t ldr, int64_t N, int dpad, const float* y, const float* W, int ldw,

@@ -7,7 +7,12 @@ dictionaries), ``MimeTypeDetector.scala`` (Tika) and ``PhoneNumberParser.scala``
 
 Word2Vec (skip-gram with negative sampling) and LDA (batch variational Bayes) are trained with
 dense tensor ops on the engine device (embedding gathers + batched GEMMs); LDA on a wide, mostly zero device
-matrix runs its E-step over the non-zeros instead (``ops/lda.py``, HIP). The JVM NLP libraries and
+matrix runs its E-step over the non-zeros instead (``ops/lda.py``, HIP). Word2Vec has a second trainer,
+``trainer="windows"`` (``ops/word2vec.py``, HIP): whole skip-gram windows from token ids on MFMA tiles, the
+negatives shared by a window, minibatch-synchronous and bitwise reproducible for a seed; ``"auto"`` takes it for
+a large corpus in a dataset on the device, and the model's transform then averages on the device too. Token
+lists are host-resident: such a column counts as a device column when its dataset lives on the device. The
+``"pairs"`` trainer is the autograd one over materialised (centre, context) pairs. The JVM NLP libraries and
 their model binaries / dictionaries are not available (the reference mount also lacks the large
 blobs, ``.MISSING_LARGE_BLOBS``); the detectors here are compact, documented replacements whose exact
 outputs are "parity unpinned".
@@ -27,6 +32,7 @@ from ...data.columns import NumericColumn, ObjectColumn, TextColumn, VectorColum
 from ...data.vector_metadata import OpVectorColumnMetadata, OpVectorMetadata
 from ...features import types as T
 from ...ops import lda as LDA
+from ...ops import word2vec as W2V
 from ...utils import text as TU
 from ..base import UnaryEstimator, UnaryTransformer, register_stage
 from .text_stages import detect_mime, is_valid_phone
@@ -154,8 +160,15 @@ class OpWord2VecModel(_ListVectorModel):
     def transform_columns(self, *cols, ds=None):
         dev = cols[0].device
         dim = self.vectors.shape[1]
-        rows = [self._row(v) for v in cols[0].to_list()]
-        X = torch.as_tensor(np.stack(rows) if rows else np.zeros((0, dim)), dtype=vector_dtype(dev), device=dev)
+        docs = cols[0].to_list()
+        tdev = _token_device(cols[0], ds)
+        if self.vocabulary and W2V.worthwhile(tdev, None, sum(len(d or ()) for d in docs)):
+            # document means on the device (ops/csrc/hip/w2v_kernels.hip), in the device's vector dtype
+            corpus = W2V.TokenCorpus.from_docs(docs, {t: i for i, t in enumerate(self.vocabulary)}, tdev)
+            X = W2V.doc_mean(corpus, torch.from_numpy(self.vectors)).to(vector_dtype(tdev))
+        else:
+            rows = [self._row(v) for v in docs]
+            X = torch.as_tensor(np.stack(rows) if rows else np.zeros((0, dim)), dtype=vector_dtype(dev), device=dev)
         tf = self.get_transient_features()[0]
         self.metadata["vector_metadata"] = self.vector_metadata([col_meta(tf, descriptor=f"w2v_{i}")
                                                                  for i in range(dim)])
@@ -178,14 +191,38 @@ class OpWord2VecModel(_ListVectorModel):
         self.vectors = np.asarray(a["vectors"], np.float32)
 
 
+def _token_device(c, ds) -> torch.device:
+    """Where a token-list column lives: the lists themselves are host-resident, the device is its dataset's."""
+    return ds.device if ds is not None and ds.device.type == "cuda" else c.device
+
+
 @register_stage
 class OpWord2Vec(VectorizerMixin, UnaryEstimator):
     """Skip-gram word vectors (negative sampling) trained on the device; a document vector is the mean
-    of its word vectors (Spark ``Word2VecModel.transform``)."""
+    of its word vectors (Spark ``Word2VecModel.transform``). ``trainer``: ``"pairs"`` (autograd over materialised
+    pairs, ``batch_size`` pairs a step), ``"windows"`` (``ops/word2vec.py``: HIP, a device column, ``window_size <=
+    8``, ``num_negative <= 15``, ``vector_size <= 256``, ``batch_size`` windows a step) or ``"auto"``."""
     operation_name = "word2Vec"
     output_type = T.OPVector
     _defaults = {"vector_size": 100, "window_size": 5, "min_count": 5, "max_iter": 1, "step_size": 0.025,
-                 "num_negative": 5, "seed": 0, "batch_size": 4096}
+                 "num_negative": 5, "seed": 0, "batch_size": 4096, "trainer": "auto"}
+
+    def _use_windows(self, c, ds, n_tokens: int) -> bool:
+        p = self.params
+        if p["trainer"] not in ("auto", "pairs", "windows"):
+            raise ValueError(f"trainer must be auto, pairs or windows, got {p['trainer']!r}")
+        if p["trainer"] == "auto":
+            return W2V.worthwhile(_token_device(c, ds), p, n_tokens)
+        if p["trainer"] == "windows":
+            bad = W2V.limit_violated(p["vector_size"], p["window_size"], p["num_negative"])
+            if bad is None and _token_device(c, ds).type != "cuda":
+                bad = "the column must be in a dataset on the device"
+            if bad:
+                raise ValueError(f'trainer="windows": {bad}')
+            from ...ops import _native
+            _native.hip()                           # a library that cannot be loaded is an error, not a pairs run
+            return True
+        return False
 
     def fit_columns(self, c, ds=None):
         p = self.params
@@ -196,6 +233,10 @@ class OpWord2Vec(VectorizerMixin, UnaryEstimator):
         if not vocab:
             return OpWord2VecModel([], np.zeros((0, dim), np.float32))
         idx = {t: i for i, t in enumerate(vocab)}
+        if self._use_windows(c, ds, sum(cnt[t] for t in vocab)):
+            corpus = W2V.TokenCorpus.from_docs(docs, idx, _token_device(c, ds))
+            emb = W2V.train(corpus, [cnt[t] for t in vocab], p)
+            return OpWord2VecModel(vocab, emb[:, :dim].cpu().numpy())
         dev = torch.device("cuda") if torch.cuda.is_available() and c.device.type == "cuda" else torch.device("cpu")
         pairs = []
         w = int(p["window_size"])
