@@ -53,21 +53,28 @@ class BatchedObjective:
         self.passes = 0
         # fused one-pass HIP objective (ops/csrc/hip/linear_kernels.hip) when X is an fp32 device matrix
         self.fused = LK.fused_objective_supported(X) and loss in LK.LOSS_CODES
+        # a sparse design: margins from the CSR non-zeros, loss and sums in one launch (sparse_lr_kernels.hip)
+        self.sparse = LK.sparse_fused_supported(X, loss) and LK.sparse_fused_enabled()
+        self.fused = self.fused or self.sparse
         if self.fused:
             self.yf = y.to(device=X.device, dtype=torch.float32).contiguous()
-            self.Wf = W.to(torch.float32).contiguous()
+            # the sparse pass reads only the distinct weight columns (Wb below): no fp32 copy of all of W
+            self.Wf = None if self.sparse else W.to(torch.float32).contiguous()
             self.ysf = None if y_scale is None else y_scale.to(device=X.device, dtype=torch.float32)
         # bf16 design copy on the bf16 matrix cores (ops/csrc/hip/linear_bf16_kernels.hip) when configured
         from .. import config as _cfg
         self.bf16 = LK.Bf16Design.of(X) if (self.fused and _cfg.linear_dtype() == "bf16"
                                             and LK.Bf16Design.supported(X)) else None
-        if self.bf16 is not None:
+        if self.bf16 is not None or self.sparse:
             # one weight column per distinct training-row set (wcols: _weight_columns of the jobs), mapped per problem
             P = W.shape[1]
             wc = list(range(P)) if wcols is None else list(wcols)
             uniq = sorted(set(wc))
             pos = {c: i for i, c in enumerate(uniq)}
-            self.Wb = self.Wf if len(uniq) == P else self.Wf[:, uniq].contiguous()
+            if self.sparse:
+                self.Wb = W[:, uniq].to(torch.float32).contiguous()
+            else:
+                self.Wb = self.Wf if len(uniq) == P else self.Wf[:, uniq].contiguous()
             self.wmap = LK.weight_map([pos[c] for c in wc], P, X.device)
 
     def _pass_body(self, U, grad):
@@ -76,6 +83,9 @@ class BatchedObjective:
         if self.bf16 is not None:
             return LK.fused_objective_bf16(self.bf16, self.yf, self.Wb, V, b, self.loss, self.ysf, grad=grad,
                                            wmap=self.wmap)
+        if self.sparse:
+            return LK.sparse_fused_objective(self.X, self.yf, self.Wb, V, b, self.loss, self.ysf, grad=grad,
+                                             wmap=self.wmap)
         return LK.fused_objective(self.X, self.yf, self.Wf, V, b, self.loss, self.ysf, grad=grad)
 
     def _fused_pass(self, U, grad):

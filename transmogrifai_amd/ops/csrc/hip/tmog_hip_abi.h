@@ -177,6 +177,20 @@ int tmog_hip_softmax_epilogue(float* M, int64_t N, int P, int K, const float* bi
                               int ldw, float* Lw, int grad, hipStream_t stream);
 int tmog_hip_colsum(const float* R, int64_t N, int C, int nblk, double* part, hipStream_t stream);
 
+// ---- hip/sparse_lr_kernels.hip: the fused binary objective on a sparse design (CSR of the sparse columns with
+// Vs [ds][ldv], dense block Xd [N][nd] with Vd [nd][ldv], nd <= tmog_hip_sparse_lr_nd_max(); Xd null: no dense block
+// in the kernel, madd [N][ldm] -- or null -- is added to the margins instead). Problem p weighs row i by
+// W[i][wmap[p]]. f_part / r_part hold nblk x ceil(P / chunk) x chunk doubles, chunk = tmog_hip_sparse_lr_chunk(P);
+// f [P] and r [P] are their sums in a fixed order; R [N][ldr] is written only with grad
+int tmog_hip_sparse_lr_nd_max();
+int tmog_hip_sparse_lr_chunk(int P);
+int tmog_hip_sparse_lr_objective(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t N,
+                                 const float* Vs, int ldv, const float* Xd, int nd, const float* Vd,
+                                 const float* madd, int ldm, const float* y, const float* W, int ldw,
+                                 const int32_t* wmap, int P, const float* bias, int loss, const float* yscale,
+                                 int grad, float* R, int ldr, double* f_part, double* r_part, int nblk, double* f,
+                                 double* r, hipStream_t stream);
+
 // ---- hip/stats_kernels.hip
 int tmog_hip_class_colsum(const float* X, int64_t n, int d, int64_t ld, const int32_t* codes, int P, int L,
                           double* out, hipStream_t stream);

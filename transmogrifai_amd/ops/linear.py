@@ -3,6 +3,12 @@
 ``gemm``/``gemm_t`` are the two halves of every linear-model iteration (``M = X V`` and
 ``G = X^T R``); on device they run on the matrix cores (hipBLASLt via torch for these plain
 library-shaped GEMMs, fp32 in / fp32 accumulate), on the host through BLAS.
+
+What runs where on the device: a dense fp32 design up to 384 columns -- ``fused_objective``
+(``linear_kernels.hip``, one pass), up to 2048 -- library GEMM + ``lr_epilogue_grad``; its bf16 copy --
+``fused_objective_bf16`` / ``mnl_objective_bf16``; a :class:`SparseDesign` -- products on ``sparse_kernels.hip``,
+the multinomial epilogue ``softmax_objective``, the binary objective ``sparse_fused_objective``
+(``sparse_lr_kernels.hip``: margins, loss and sums in one launch, ``X^T R`` on ``csc_spmm_t_kernel``).
 """
 from __future__ import annotations
 
@@ -196,6 +202,74 @@ def fused_objective_supported(X) -> bool:
         return False
     return X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and 1 <= X.shape[1] <= _LR_WIDE_DMAX \
         and X.is_contiguous()
+
+
+def sparse_fused_supported(D, loss: str) -> bool:
+    """The fused HIP objective of a sparse design (``sparse_fused_objective``) handles a :class:`SparseDesign` on
+    the GPU and the losses of ``LOSS_CODES``."""
+    return isinstance(D, SparseDesign) and D.device.type == "cuda" and loss in LOSS_CODES
+
+
+def sparse_fused_enabled() -> bool:
+    """``TMOG_LR_SPARSE_FUSED=0`` restores the unfused pass (CSR product, library GEMM of the dense block and the
+    torch elementwise epilogue over ``[N, P]``). On by default: at 1M x 1352, 40 non-zeros a row, 24 problems the
+    fused value pass measured 0.73 ms against 1.33 ms, value + gradient 2.82 against 3.60 ms and a binary
+    ``OpLogisticRegression.fit_batch`` 82 against 99 ms (profiles/sparse_binary_objective.txt)."""
+    return os.environ.get("TMOG_LR_SPARSE_FUSED", "1") != "0"
+
+
+def sparse_lr_pass(D: "SparseDesign", y: torch.Tensor, W: torch.Tensor, V: torch.Tensor, bias: torch.Tensor,
+                   loss: str, yscale=None, grad: bool = True, wmap: Optional[torch.Tensor] = None,
+                   R: Optional[torch.Tensor] = None):
+    """One launch of ``ops/csrc/hip/sparse_lr_kernels.hip`` for the ``P = V.shape[1]`` problems: the margins
+    ``m = X V + bias`` row by row from the CSR non-zeros and the dense block, their losses and the fp64 sums, without
+    an ``[N, P]`` margin array. Returns ``(f [P], r [P], R)`` with ``f = sum_i W l(m)``, ``r = sum_i W l'(m)`` in fp64
+    and, with ``grad``, ``R [N, P] = W l'(m)`` in fp32 (written into the caller's ``R`` when given: fp32, unit column
+    stride); a value pass writes nothing per row. Problem p's row weights are column ``wmap[p]`` of ``W`` (device
+    int32; default column p). A dense block wider than the kernel keeps in LDS (``tmog_hip_sparse_lr_nd_max``) is
+    multiplied by the library GEMM and enters the kernel as an addend."""
+    from . import _native as N_
+    lib = N_.hip()
+    dev = D.device
+    N = int(D.shape[0])
+    P = int(V.shape[1])
+    V = V.to(device=dev, dtype=torch.float32)
+    Vs = V.index_select(0, D.idx_s).contiguous()
+    nd = int(D.idx_d.numel())
+    Vd = V.index_select(0, D.idx_d).contiguous()
+    Xd, madd = (D.Xd if nd else None), None
+    if nd > int(lib.tmog_hip_sparse_lr_nd_max()):
+        Xd, madd = None, (D.Xd @ Vd).contiguous()
+    yf = y.to(device=dev, dtype=torch.float32).contiguous()
+    Wf = W.to(torch.float32).contiguous()
+    if wmap is None:
+        wmap = torch.arange(P, dtype=torch.int32, device=dev)
+    bf = bias.to(device=dev, dtype=torch.float32).contiguous()
+    ys = None if yscale is None else yscale.to(device=dev, dtype=torch.float32).contiguous()
+    chunk = int(lib.tmog_hip_sparse_lr_chunk(P))
+    # persistent workgroups of 4 waves, 64 / chunk rows a wave at a time: up to 8 per CU, each with work
+    groups = (N + 64 // chunk - 1) // (64 // chunk)
+    nblk = max(1, min((groups + 3) // 4, torch.cuda.get_device_properties(dev).multi_processor_count * 8))
+    part = torch.empty(2, nblk, (P + chunk - 1) // chunk * chunk, dtype=torch.float64, device=dev)
+    fr = torch.empty(2, P, dtype=torch.float64, device=dev)     # the partials, folded in a fixed order by the launch
+    if grad and R is None:
+        R = torch.empty(N, P, dtype=torch.float32, device=dev)
+    if R is not None and not (R.dtype == torch.float32 and R.shape == (N, P) and R.stride(1) == 1):
+        raise ValueError("sparse_lr_pass: R must be fp32 [N, P] with unit column stride")
+    N_.check(lib.tmog_hip_sparse_lr_objective(
+        N_.ptr(D.row_ptr), N_.ptr(D.col), N_.ptr(D.val), N, N_.ptr(Vs), P, N_.ptr(Xd), nd, N_.ptr(Vd),
+        N_.ptr(madd), P, N_.ptr(yf), N_.ptr(Wf), Wf.shape[1], N_.ptr(wmap), P, N_.ptr(bf), LOSS_CODES[loss],
+        N_.ptr(ys), int(grad), N_.ptr(R), 0 if R is None else R.stride(0), N_.ptr(part[0]), N_.ptr(part[1]), nblk,
+        N_.ptr(fr[0]), N_.ptr(fr[1]), N_.stream(dev)), "sparse_lr_objective")
+    return fr[0], fr[1], (R if grad else None)
+
+
+def sparse_fused_objective(D: "SparseDesign", y: torch.Tensor, W: torch.Tensor, V: torch.Tensor, bias: torch.Tensor,
+                           loss: str, yscale=None, grad: bool = True, wmap: Optional[torch.Tensor] = None):
+    """``fused_objective`` on a sparse design: ``(f [P], r [P], G [d, P] or None)`` in fp64, ``G`` in the original
+    column order. ``f``, ``r`` and ``R`` come from one ``sparse_lr_pass``; ``G = D.tmm(R)``."""
+    f, r, R = sparse_lr_pass(D, y, W, V, bias, loss, yscale, grad, wmap)
+    return f, r, (D.tmm(R) if grad else None)
 
 
 def _n_blocks(N: int, grad: bool = True) -> int:
