@@ -81,17 +81,23 @@ class GeneralizedLinearRegressionLearner(Learner):
             groups.setdefault((fam, link, float(j.params.get("variance_power", 0.0)),
                                j.params.get("link_power")), []).append(i)
         res = [None] * len(jobs)
+        # a wide, mostly-zero matrix: one sparse design for every group (ops/linear.py SparseDesign.wgram / mm64)
+        from ..ops import linear as LK
+        from .linear import _row_par
+        D = LK.sparse_gram_design(X) if _row_par(context) is None else None
         for (fam, link, vp, lp), idxs in groups.items():
             sub = [jobs[i] for i in idxs]
-            for i, r in zip(idxs, self._irls(X, y, sub, fam, link, vp, lp)):
+            for i, r in zip(idxs, self._irls(X, y, sub, fam, link, vp, lp, D)):
                 res[i] = r
         return res
 
-    def _irls(self, X, y, jobs, fam, link, vp, lp):
+    def _irls(self, X, y, jobs, fam, link, vp, lp, D=None):
+        """``D``: the sparse design of ``X`` -- the Grams come from ``D.wgram`` and the margins from ``D.mm64``, and
+        no fp64 copy of ``X`` is made."""
         dev = X.device
         N, d = X.shape
         P = len(jobs)
-        Xd = X.to(torch.float64)
+        Xd = X.to(torch.float64) if D is None else None
         yd = y.to(torch.float64)
         W0 = torch.zeros(N, P, dtype=torch.float64, device=dev)
         for p, j in enumerate(jobs):
@@ -106,9 +112,15 @@ class GeneralizedLinearRegressionLearner(Learner):
         link_power = (1.0 - vp) if (fam == "tweedie" and lp is None) else (lp or 0.0)
         g, ginv, gprime = _link(link, link_power)
         var = FAMILIES[fam][0]
-        Xa = torch.cat([Xd, torch.ones(N, 1, dtype=torch.float64, device=dev)], 1)     # [N, d+1]
         from ..ops.stats import weighted_gram
-        Xg = X if (X.is_cuda and X.dtype == torch.float32) else Xd      # the Gram kernel widens fp32 itself
+        if D is None:
+            Xa = torch.cat([Xd, torch.ones(N, 1, dtype=torch.float64, device=dev)], 1)     # [N, d+1]
+            Xg = X if (X.is_cuda and X.dtype == torch.float32) else Xd      # the Gram kernel widens fp32 itself
+        else:                   # the same Grams from the non-zeros; the margins below from D.mm64
+            Xa = Xg = None
+
+            def weighted_gram(_, W, Y=None):
+                return D.wgram(W, Y)
         # weighted column sums and sums of squares of every problem: row d and the diagonal of [X | 1]'s Gram
         G0 = weighted_gram(Xg, W0)
         wsum = W0.sum(0).clamp_min(1e-300)
@@ -142,7 +154,7 @@ class GeneralizedLinearRegressionLearner(Learner):
             nb = torch.linalg.solve(A + 1e-12 * torch.eye(d + 1, dtype=torch.float64, device=dev), b).t()
             delta = (nb - beta).abs().max()
             beta = nb
-            mu = ginv(Xa @ beta)
+            mu = ginv(Xa @ beta if D is None else D.mm64(beta[:d], beta[d]))
             if fam == "binomial":
                 mu = mu.clamp(1e-12, 1 - 1e-12)
             elif fam in ("poisson", "gamma", "tweedie"):

@@ -363,6 +363,10 @@ def _weighted_grams(X, y, jobs, par=None, chunk: int = 1 << 18):
         X, W, yd = X[sl], W[sl], yd[sl]
         N = int(X.shape[0])
     from ..ops.stats import weighted_gram
+    # a wide, mostly-zero matrix: the same Grams from its non-zeros (ops/linear.py SparseDesign.wgram)
+    D = LK.sparse_gram_design(X) if par is None else None
+    if D is not None:
+        return D.wgram(W, yd), group
     # fp64 matrix-core Grams of [X | 1 | y] for every fold-weight column in one pass (stats_kernels.hip wgram)
     G = weighted_gram(X, W, yd, chunk=chunk)
     G = _psum(par, G)[0]

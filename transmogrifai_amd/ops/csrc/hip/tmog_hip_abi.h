@@ -191,6 +191,32 @@ int tmog_hip_sparse_lr_objective(const int64_t* row_ptr, const int32_t* col, con
                                  int grad, float* R, int ldr, double* f_part, double* r_part, int nblk, double* f,
                                  double* r, hipStream_t stream);
 
+// ---- hip/sparse_gram_kernels.hip: fp64 weighted Grams and margins of a sparse design (ops/linear.py SparseDesign:
+// CSR row_ptr / col / val and segmented CSC seg_begin / csc_row / csc_val / col_seg of the ds sparse columns, dense
+// block Xd [N][dd]). tmog_hip_sparse_wgram writes, for k < K, every row and column of G [K][D][D] (D = ds + dd + 1,
+// + 1 with Y) that belongs to a sparse column: G_k = A_k^T diag(W[:, k]) A_k, A_k = [X | 1 | Y_k] (Y [N][ldy], column
+// k with per_weight, else column 0; null: no response column). pos [ds + dd + 1 (+ 1)] is the row / column of G of
+// the sparse columns, then the dense columns, then the 1 and Y columns; the block of the latter three is the caller's.
+// An item is `nslice` segments of one column: item_col / item_seg [n_items] (column, first segment; columns ascending)
+// and col_item [ds + 1] (first item of a column). wp <= tmog_hip_sparse_wgram_width_max() positions are served in
+// one pass (wider blocks in ranges of wp), dd <= tmog_hip_sparse_wgram_dd_max(), and the partial buffer
+// n_items x tmog_hip_sparse_wgram_kw() x wp doubles stays within tmog_hip_sparse_wgram_part_bytes().
+// tmog_hip_sparse_margin_f64 writes eta [N][lde] (columns < P) = Xs Bs + Xd Bd + b0 with Bs [ds][ldb], Bd [dd][ldb],
+// b0 [P] or null, all fp64
+int tmog_hip_sparse_wgram_kw();
+int tmog_hip_sparse_wgram_width_max();
+int tmog_hip_sparse_wgram_dd_max();
+int64_t tmog_hip_sparse_wgram_part_bytes();
+int tmog_hip_sparse_wgram(const int64_t* seg_begin, const int32_t* csc_row, const float* csc_val,
+                          const int64_t* col_seg, const int32_t* item_col, const int64_t* item_seg,
+                          const int64_t* col_item, int64_t n_items, int nslice, const int64_t* row_ptr,
+                          const int32_t* col, const float* val, int64_t N, int ds, const float* Xd, int dd,
+                          const double* W, int64_t ldw, int K, const double* Y, int64_t ldy, int per_weight,
+                          const int32_t* pos, int wp, double* G, hipStream_t stream);
+int tmog_hip_sparse_margin_f64(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t N,
+                               const double* Bs, int ldb, const float* Xd, int dd, const double* Bd, const double* b0,
+                               int P, double* eta, int64_t lde, hipStream_t stream);
+
 // ---- hip/stats_kernels.hip
 int tmog_hip_class_colsum(const float* X, int64_t n, int d, int64_t ld, const int32_t* codes, int P, int L,
                           double* out, hipStream_t stream);

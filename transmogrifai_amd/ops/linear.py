@@ -8,7 +8,9 @@ What runs where on the device: a dense fp32 design up to 384 columns -- ``fused_
 (``linear_kernels.hip``, one pass), up to 2048 -- library GEMM + ``lr_epilogue_grad``; its bf16 copy --
 ``fused_objective_bf16`` / ``mnl_objective_bf16``; a :class:`SparseDesign` -- products on ``sparse_kernels.hip``,
 the multinomial epilogue ``softmax_objective``, the binary objective ``sparse_fused_objective``
-(``sparse_lr_kernels.hip``: margins, loss and sums in one launch, ``X^T R`` on ``csc_spmm_t_kernel``).
+(``sparse_lr_kernels.hip``: margins, loss and sums in one launch, ``X^T R`` on ``csc_spmm_t_kernel``), the
+regression learners' fp64 weighted Grams ``SparseDesign.wgram`` and IRLS margins ``SparseDesign.mm64``
+(``sparse_gram_kernels.hip``: the Gram's sparse rows from the non-zeros, the dense block's on ``wgram_kernel``).
 """
 from __future__ import annotations
 
@@ -161,6 +163,127 @@ class SparseDesign:
                 Gs[:, c0:c1] = Gc
             G[self.idx_s] = Gs
         return G
+
+    def _gram_items(self, wp: int):
+        """The work items of ``sparse_wgram_kernel`` for a pass width of ``wp`` positions: runs of ``nslice`` CSC
+        segments of one column, ``nslice`` the smallest power of two at which the partial buffer
+        (items x KW x wp doubles) stays within the kernel's cap; every non-empty column has at least one item.
+        ``(item_col, item_seg, col_item, n_items, nslice)``, made once per width."""
+        from . import _native as N_
+        cache = self.__dict__.setdefault("_gram_item_cache", {})
+        if wp not in cache:
+            lib, dev = N_.hip(), self.device
+            max_items = int(lib.tmog_hip_sparse_wgram_part_bytes()) // (8 * int(lib.tmog_hip_sparse_wgram_kw()) * wp)
+            nseg = self.col_seg[1:] - self.col_seg[:-1]
+            nseg_h = nseg.cpu()
+            nslice = 1
+            while int(((nseg_h + nslice - 1) // nslice).sum()) > max_items:
+                nslice *= 2
+            nit = (nseg + nslice - 1) // nslice
+            col_item = torch.zeros(self.ds + 1, dtype=torch.int64, device=dev)
+            col_item[1:] = torch.cumsum(nit, 0)
+            n_items = int(((nseg_h + nslice - 1) // nslice).sum())
+            item_col = torch.repeat_interleave(torch.arange(self.ds, device=dev), nit)
+            item_seg = self.col_seg[item_col] + (torch.arange(n_items, device=dev) - col_item[item_col]) * nslice
+            cache[wp] = (item_col.to(torch.int32).contiguous(), item_seg.contiguous(), col_item, n_items, nslice)
+        return cache[wp]
+
+    def wgram(self, W: torch.Tensor, Y: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[K, D, D]`` fp64 weighted Grams ``A_k^T diag(W[:, k]) A_k``, ``A_k = [X | 1 | Y_k]``, columns in the
+        original order: the contract of ``ops.stats.weighted_gram`` (``Y`` None, ``[n]`` or ``[n, K]``), taken from
+        the non-zeros. The dense side ``[Xd | 1 | Y_k]``'s own block comes from ``weighted_gram`` on the dense block
+        (a few fp64 sums without one); every row and column of a sparse column from ``sparse_wgram_kernel`` and its
+        fold (``ops/csrc/hip/sparse_gram_kernels.hip``). Exactly symmetric; ``out`` (contiguous fp64 ``[K, D, D]``)
+        is overwritten in full when given."""
+        from . import _native as N_
+        from .stats import weighted_gram
+        lib, dev = N_.hip(), self.device
+        N, d = self.shape
+        K = int(W.shape[1])
+        hasy = Y is not None
+        per_weight = hasy and Y.dim() == 2
+        if per_weight and int(Y.shape[1]) != K:
+            raise ValueError("Y must be [n] or [n, K]")
+        dd, ds = int(self.idx_d.numel()), self.ds
+        De, D = dd + 1 + int(hasy), d + 1 + int(hasy)
+        if not sparse_wgram_supported(self) or K <= 0:
+            raise ValueError("SparseDesign.wgram: unsupported design (sparse_wgram_supported)")
+        Wd = W.to(device=dev, dtype=torch.float64).contiguous()
+        Yd = None if not hasy else Y.to(device=dev, dtype=torch.float64).contiguous()
+        G = torch.empty(K, D, D, dtype=torch.float64, device=dev) if out is None else out
+        if not (G.dtype == torch.float64 and G.shape == (K, D, D) and G.is_contiguous()):
+            raise ValueError("SparseDesign.wgram: out must be contiguous fp64 [K, D, D]")
+        if dd:
+            Ge = weighted_gram(self.Xd, Wd, Yd)
+        else:                                   # E = [1 | y_k]
+            Ge = torch.empty(K, De, De, dtype=torch.float64, device=dev)
+            Ge[:, 0, 0] = Wd.sum(0)
+            if hasy:
+                Yk = Yd if per_weight else Yd[:, None]
+                wy = Wd * Yk
+                Ge[:, 0, 1] = Ge[:, 1, 0] = wy.sum(0)
+                Ge[:, 1, 1] = (wy * Yk).sum(0)
+        side = torch.cat([self.idx_d, torch.arange(d, D, device=dev)])
+        G[:, side[:, None], side[None, :]] = Ge
+        if ds:
+            # one pass serves wp positions; narrower when the columns' one item each would not fit the partial cap
+            wp = min(ds + De, int(lib.tmog_hip_sparse_wgram_width_max()))
+            per_pos = 8 * int(lib.tmog_hip_sparse_wgram_kw()) * max(int((self.col_seg[1:] > self.col_seg[:-1]).sum()), 1)
+            while per_pos * wp > int(lib.tmog_hip_sparse_wgram_part_bytes()):
+                wp = (wp + 1) // 2
+            item_col, item_seg, col_item, n_items, nslice = self._gram_items(wp)
+            pos = torch.cat([self.idx_s, side]).to(torch.int32).contiguous()
+            N_.check(lib.tmog_hip_sparse_wgram(
+                N_.ptr(self.seg_begin), N_.ptr(self.csc_row), N_.ptr(self.csc_val), N_.ptr(self.col_seg),
+                N_.ptr(item_col), N_.ptr(item_seg), N_.ptr(col_item), n_items, nslice, N_.ptr(self.row_ptr),
+                N_.ptr(self.col), N_.ptr(self.val), N, ds, N_.ptr(self.Xd) if dd else None, dd, N_.ptr(Wd), K, K,
+                N_.ptr(Yd), (K if per_weight else 1) if hasy else 0, int(per_weight), N_.ptr(pos), wp, N_.ptr(G),
+                N_.stream(dev)), "sparse_wgram")
+        return G
+
+    def mm64(self, B: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``X B + bias`` in fp64, ``[N, P]``, from the CSR non-zeros and the dense block (``sparse_gram_kernels.hip``
+        ``sparse_margin_f64_kernel``): ``B [d, P]`` and ``bias [P]`` fp64, fp64 sums in a fixed order, no fp64 copy
+        of the matrix."""
+        from . import _native as N_
+        dev = self.device
+        N, P = int(self.shape[0]), int(B.shape[1])
+        B = B.to(device=dev, dtype=torch.float64)
+        dd = int(self.idx_d.numel())
+        Bs = B.index_select(0, self.idx_s).contiguous()
+        Bd = B.index_select(0, self.idx_d).contiguous()
+        b0 = None if bias is None else bias.to(device=dev, dtype=torch.float64).contiguous()
+        eta = torch.empty(N, P, dtype=torch.float64, device=dev)
+        if N and P:
+            N_.check(N_.hip().tmog_hip_sparse_margin_f64(
+                N_.ptr(self.row_ptr), N_.ptr(self.col), N_.ptr(self.val), N, N_.ptr(Bs), P,
+                N_.ptr(self.Xd) if dd else None, dd, N_.ptr(Bd) if dd else None, N_.ptr(b0), P, N_.ptr(eta), P,
+                N_.stream(dev)), "sparse_margin_f64")
+        return eta
+
+
+_WGRAM_DS_MAX = 16384   # sparse columns: one item each within the partial cap at a pass width of 256 positions
+
+
+def sparse_wgram_supported(D) -> bool:
+    """``SparseDesign.wgram`` / ``mm64`` serve a :class:`SparseDesign` on the GPU whose dense block is within
+    ``tmog_hip_sparse_wgram_dd_max()`` columns (wider: the dense Gram is the better tool) and whose sparse block is
+    within ``_WGRAM_DS_MAX``; a block wider than ``tmog_hip_sparse_wgram_width_max()`` runs in column ranges."""
+    from . import _native as N_
+    return isinstance(D, SparseDesign) and D.device.type == "cuda" and D.shape[0] > 0 and D.ds <= _WGRAM_DS_MAX \
+        and int(D.idx_d.numel()) <= int(N_.hip().tmog_hip_sparse_wgram_dd_max())
+
+
+def sparse_gram_design(X) -> Optional["SparseDesign"]:
+    """The :class:`SparseDesign` whose ``wgram`` / ``mm64`` replace the dense fp64 Gram and margins of the regression
+    learners, or None: an fp32 device matrix that is ``SparseDesign.worthwhile`` and ``sparse_wgram_supported``.
+    ``TMOG_LINREG_SPARSE=0`` keeps the dense Gram."""
+    if os.environ.get("TMOG_LINREG_SPARSE", "1") == "0" or not isinstance(X, torch.Tensor) \
+            or X.dtype != torch.float32 or not SparseDesign.worthwhile(X):
+        return None
+    D = SparseDesign(X)
+    return D if sparse_wgram_supported(D) else None
 
 
 def softmax_objective(M: torch.Tensor, y: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, P: int, K: int,
