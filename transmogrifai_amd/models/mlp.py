@@ -20,6 +20,11 @@ shapes, see ``ops/dense.py enabled``); ``TMOG_DENSE_MFMA=1`` selects the fused m
 Spark stacks rows into ``blockSize`` matrices only for BLAS; here all rows of a fold are one batch. The
 objective is the weighted mean cross-entropy (no regularisation, as Spark's MLP). The host path computes the
 same objective with torch ops.
+
+On a wide, mostly-zero matrix (``ops/linear.py`` ``SparseDesign``) with one or two hidden layers of up to 64 units and
+up to 16 classes, ``TMOG_MLP_SPARSE_FUSED=1`` runs the whole pass in one kernel from the CSR non-zeros
+(``ops/csrc/hip/sparse_mlp_kernels.hip``, ``ops.linear.sparse_mlp_pass``): no layer array exists but the first
+layer's ``dZ1``, whose ``X^T dZ1`` is ``SparseDesign.tmm``.
 """
 from __future__ import annotations
 
@@ -72,8 +77,10 @@ class MLPObjective:
     ``W [N, P]``), as ``linear.owlqn_batched`` expects: ``value(U)`` / ``value_grad(U)`` with ``U [n_params, P]``
     (per layer: the ``a x b`` weights row-major, then the ``b`` biases)."""
 
-    def __init__(self, X: torch.Tensor, y: torch.Tensor, W: torch.Tensor, layers: Sequence[int]):
-        self.X = X.to(torch.float32).contiguous()
+    def __init__(self, X, y: torch.Tensor, W: torch.Tensor, layers: Sequence[int]):
+        from ..ops.linear import SparseDesign
+        self.sparse = isinstance(X, SparseDesign)       # the whole pass on sparse_mlp_kernels.hip
+        self.X = X if self.sparse else X.to(torch.float32).contiguous()
         self.N = int(X.shape[0])
         self.yi = y.to(device=X.device, dtype=torch.int64)
         self.yf = self.yi.to(torch.float32).contiguous()
@@ -113,8 +120,22 @@ class MLPObjective:
         R[torch.arange(N, device=Z.device), :, self.yi.clamp(0, K - 1)] -= 1.0
         return f, (R * self.W[..., None]).permute(1, 0, 2)
 
+    def _pass_sparse(self, U: torch.Tensor, grad: bool):
+        from ..ops import linear as LK
+        f, tail, db1, dW1, _ = LK.sparse_mlp_pass(self.X, self.yf, self.W, self._unpack(U), self.wsum, grad)
+        if not grad:
+            return f, None
+        P = U.shape[1]
+        g = torch.empty_like(U)
+        for (o, a, b, ob), (dW, db) in zip(self.slices, [(dW1, db1)] + tail):
+            g[o:o + a * b] = dW.reshape(P, a * b).t().to(U.dtype)
+            g[ob:ob + b] = db.t().to(U.dtype)
+        return f, g
+
     def _pass(self, U: torch.Tensor, grad: bool):
         self.passes += 1
+        if self.sparse:
+            return self._pass_sparse(U, grad)
         params = self._unpack(U)
         acts = []
         H = None
@@ -181,7 +202,7 @@ class MultilayerPerceptronClassifierLearner(Learner):
                 "solver": "l-bfgs", "block_size": 128}
 
     def fit_batch(self, X, y, jobs, context=None) -> List[dict]:
-        from .linear import _fold_weights, owlqn_batched
+        from .linear import _fold_weights, _row_par, owlqn_batched
         K = int(y.max().item()) + 1 if y.numel() else 2
         K = max(K, 2)
         dev = X.device
@@ -194,10 +215,17 @@ class MultilayerPerceptronClassifierLearner(Learner):
             layer_of.append(layers)
             groups.setdefault(tuple(layers), []).append(i)
         out: List[dict] = [None] * len(jobs)
+        # a wide, mostly-zero matrix: one SparseDesign per fit, shared by the layer groups it serves
+        from ..ops import linear as LK
+        design = None
+        small = any(len(l) in (3, 4) and max(l[1:-1]) <= 64 and l[-1] <= 16 for l in groups)
+        if small and _row_par(context) is None and LK.sparse_mlp_enabled() and LK.SparseDesign.worthwhile(X):
+            design = LK.SparseDesign(X)
         for layers, idx in groups.items():
             gj = [jobs[i] for i in idx]
             W = _fold_weights(X.shape[0], gj, dev, torch.float32)
-            obj = MLPObjective(X, y, W, layers)
+            fused = design is not None and LK.sparse_mlp_supported(design, layers)
+            obj = MLPObjective(design if fused else X, y, W, layers)
             U0 = torch.as_tensor(np.stack([_init_params(layers, int(j.params.get("seed", 0))) for j in gj], 1),
                                  dtype=torch.float64, device=dev)
             l1 = torch.zeros_like(U0)

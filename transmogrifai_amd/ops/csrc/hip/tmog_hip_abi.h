@@ -191,6 +191,22 @@ int tmog_hip_sparse_lr_objective(const int64_t* row_ptr, const int32_t* col, con
                                  int grad, float* R, int ldr, double* f_part, double* r_part, int nblk, double* f,
                                  double* r, hipStream_t stream);
 
+// ---- hip/sparse_mlp_kernels.hip: one objective pass of P multilayer perceptrons (one or two sigmoid hidden layers
+// of width h1, h2 <= 64, h2 = 0 for one; softmax over 2 <= K <= 16 classes) on a sparse design, nd <=
+// tmog_hip_sparse_mlp_nd_max(). Per problem: W1s [ds][h1], W1d [nd][h1], b1 [h1], Wm [h1][h2], bm [h2] (h2 > 0),
+// WL [h2 or h1][K], bL [K]; row weights W[i][p], wsum [P] their sums in fp32. part holds P x nblk x 4 wave rows of
+// tmog_hip_sparse_mlp_npart(h1, h2) doubles; out [P][npart] is their sum in a fixed order: the loss sum | db1 |
+// dWm | dbm | dWL | dbL, each padded to tmog_hip_sparse_mlp_pad() of its widths (K to 16), gradients of the
+// weighted mean. Without grad only out[p][0] is written and nothing per row; with grad dZ1[i][p * h1 + j] too
+int tmog_hip_sparse_mlp_nd_max();
+int tmog_hip_sparse_mlp_pad(int width);
+int tmog_hip_sparse_mlp_npart(int h1, int h2);
+int tmog_hip_sparse_mlp_pass(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t N,
+                             const float* W1s, int ds, const float* Xd, int nd, const float* W1d, const float* b1,
+                             const float* Wm, const float* bm, const float* WL, const float* bL, const float* y,
+                             const float* W, int ldw, const float* wsum, int P, int h1, int h2, int K, int grad,
+                             float* dZ1, int64_t ldz, double* part, int nblk, double* out, hipStream_t stream);
+
 // ---- hip/sparse_gram_kernels.hip: fp64 weighted Grams and margins of a sparse design (ops/linear.py SparseDesign:
 // CSR row_ptr / col / val and segmented CSC seg_begin / csc_row / csc_val / col_seg of the ds sparse columns, dense
 // block Xd [N][dd]). tmog_hip_sparse_wgram writes, for k < K, every row and column of G [K][D][D] (D = ds + dd + 1,

@@ -10,7 +10,8 @@ What runs where on the device: a dense fp32 design up to 384 columns -- ``fused_
 the multinomial epilogue ``softmax_objective``, the binary objective ``sparse_fused_objective``
 (``sparse_lr_kernels.hip``: margins, loss and sums in one launch, ``X^T R`` on ``csc_spmm_t_kernel``), the
 regression learners' fp64 weighted Grams ``SparseDesign.wgram`` and IRLS margins ``SparseDesign.mm64``
-(``sparse_gram_kernels.hip``: the Gram's sparse rows from the non-zeros, the dense block's on ``wgram_kernel``).
+(``sparse_gram_kernels.hip``: the Gram's sparse rows from the non-zeros, the dense block's on ``wgram_kernel``), and the
+MLP classifier's whole objective pass ``sparse_mlp_pass`` (``sparse_mlp_kernels.hip``).
 """
 from __future__ import annotations
 
@@ -393,6 +394,100 @@ def sparse_fused_objective(D: "SparseDesign", y: torch.Tensor, W: torch.Tensor, 
     column order. ``f``, ``r`` and ``R`` come from one ``sparse_lr_pass``; ``G = D.tmm(R)``."""
     f, r, R = sparse_lr_pass(D, y, W, V, bias, loss, yscale, grad, wmap)
     return f, r, (D.tmm(R) if grad else None)
+
+
+_MLP_DZ1_BYTES = 1 << 30      # sparse_mlp_pass: problems per launch keep dZ1 [N, Pg * h1] fp32 within 1 GiB
+
+
+def sparse_mlp_supported(D, layers) -> bool:
+    """``sparse_mlp_pass`` serves a :class:`SparseDesign` on the GPU whose dense block is within
+    ``tmog_hip_sparse_mlp_nd_max()`` columns, one or two hidden layers of width 1..64 and 2..16 output units."""
+    from . import _native as N_
+    layers = [int(v) for v in layers]
+    return isinstance(D, SparseDesign) and D.device.type == "cuda" and D.shape[0] > 0 and len(layers) in (3, 4) \
+        and layers[0] == D.shape[1] and all(1 <= h <= 64 for h in layers[1:-1]) and 2 <= layers[-1] <= 16 \
+        and int(D.idx_d.numel()) <= int(N_.hip().tmog_hip_sparse_mlp_nd_max())
+
+
+def sparse_mlp_enabled() -> bool:
+    """``TMOG_MLP_SPARSE_FUSED=0`` keeps the dense layer products for ``OpMultilayerPerceptronClassifier`` fits on a
+    wide sparse matrix. On by default: at 1M x 1352, 40 non-zeros a row, 6 problems, layers ``[1352, 32, 6]`` a value +
+    gradient pass measured 12.1 ms against 23.3 ms and ``fit_batch`` (10 iterations, design build included) 286
+    against 367 ms; ``[1352, 64, 16, 6]`` 21.2 against 33.6 ms and 369 against 484 ms (profiles/sparse_mlp.txt)."""
+    return os.environ.get("TMOG_MLP_SPARSE_FUSED", "1") != "0"
+
+
+def sparse_mlp_pass(D: "SparseDesign", y: torch.Tensor, W: torch.Tensor, params, wsum: torch.Tensor,
+                    grad: bool = True, dZ1: Optional[torch.Tensor] = None):
+    """One objective pass of ``P`` MLPs with the same layer sizes over the sparse design, on
+    ``ops/csrc/hip/sparse_mlp_kernels.hip``: the first layer from the CSR non-zeros and the dense block, every later
+    layer, the softmax cross-entropy and the backward pass on chip. ``params`` is ``[(W_l [P, a, b], b_l [P, b])]``
+    per layer (fp32), ``W [N, P]`` the row weights, ``wsum [P]`` their sums.
+
+    Returns ``(f, tail, db1, dW1, dZ1)``: ``f [P]`` the weighted mean cross-entropy in fp64 and, with ``grad``, its
+    gradients in fp64 -- ``tail`` the ``(dW_l [P, a, b], db_l [P, b])`` of the layers after the first, ``db1 [P, h1]``,
+    ``dW1 [P, d, h1] = X^T dZ1`` from ``D.tmm`` in the original column order -- and the fp32 ``dZ1 [N, P * h1]``
+    (column ``p * h1 + j``) the kernel wrote. A value pass writes nothing per row and returns None for the rest.
+
+    Problems go through the kernel in groups that keep ``dZ1`` within ``_MLP_DZ1_BYTES`` = 1 GiB, one buffer reused
+    by every group (the returned ``dZ1`` is then the last group's). A caller's ``dZ1`` (fp32 ``[N, P * h1]``, unit
+    column stride) is written in one launch."""
+    from . import _native as N_
+    lib, dev = N_.hip(), D.device
+    N, d = int(D.shape[0]), int(D.shape[1])
+    nl = len(params)
+    P, h1 = int(params[0][0].shape[0]), int(params[0][0].shape[2])
+    h2 = int(params[1][0].shape[2]) if nl == 3 else 0
+    K = int(params[-1][0].shape[2])
+    if not sparse_mlp_supported(D, [d, h1] + ([h2] if h2 else []) + [K]) or nl not in (2, 3):
+        raise ValueError("sparse_mlp_pass: unsupported design or layer sizes (sparse_mlp_supported)")
+    if dZ1 is not None and not (dZ1.dtype == torch.float32 and dZ1.shape == (N, P * h1) and dZ1.stride(1) == 1):
+        raise ValueError("sparse_mlp_pass: dZ1 must be fp32 [N, P * h1] with unit column stride")
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    nd = int(D.idx_d.numel())
+    yf, Wf, wsf = f32(y), f32(W), f32(wsum)
+    W1 = params[0][0].to(device=dev, dtype=torch.float32)
+    h1p, h2p = int(lib.tmog_hip_sparse_mlp_pad(h1)), int(lib.tmog_hip_sparse_mlp_pad(h2))
+    npart = int(lib.tmog_hip_sparse_mlp_npart(h1, h2))
+    # persistent workgroups of 4 waves, a 16-row tile per wave at a time: two workgroups a CU over all problems
+    tiles = (N + 15) // 16
+    Pg = P if dZ1 is not None or not grad else max(1, min(P, _MLP_DZ1_BYTES // max(4 * N * h1, 1)))
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    out = torch.empty(P, npart, dtype=torch.float64, device=dev)
+    dW1 = torch.empty(P, d, h1, dtype=torch.float64, device=dev) if grad else None
+    for p0 in range(0, P, Pg):
+        p1 = min(P, p0 + Pg)
+        n = p1 - p0
+        nblk = max(1, min((tiles + 3) // 4, (2 * cus) // n))
+        part = torch.empty(n, nblk, 4, npart, dtype=torch.float64, device=dev)
+        if grad and dZ1 is None:
+            dZ1 = torch.empty(N, n * h1, dtype=torch.float32, device=dev)
+        Z = None if not grad else dZ1 if dZ1.shape[1] == n * h1 else dZ1[:, :n * h1]
+        W1s = W1[p0:p1].index_select(1, D.idx_s).contiguous()
+        W1d = W1[p0:p1].index_select(1, D.idx_d).contiguous()
+        mid = [f32(t[p0:p1]) for t in params[1]] if h2 else [None, None]
+        last = [f32(t[p0:p1]) for t in params[-1]]
+        N_.check(lib.tmog_hip_sparse_mlp_pass(
+            N_.ptr(D.row_ptr), N_.ptr(D.col), N_.ptr(D.val), N, N_.ptr(W1s), D.ds, N_.ptr(D.Xd) if nd else None, nd,
+            N_.ptr(W1d) if nd else None, N_.ptr(f32(params[0][1][p0:p1])), N_.ptr(mid[0]), N_.ptr(mid[1]),
+            N_.ptr(last[0]), N_.ptr(last[1]), N_.ptr(yf), N_.ptr(Wf[:, p0:]), Wf.shape[1], N_.ptr(wsf[p0:p1]), n, h1,
+            h2, K, int(grad), N_.ptr(Z), 0 if Z is None else Z.stride(0), N_.ptr(part), nblk, N_.ptr(out[p0:p1]),
+            N_.stream(dev)), "sparse_mlp_pass")
+        if grad:
+            dW1[p0:p1] = D.tmm(Z).view(d, n, h1).permute(1, 0, 2)
+    f = out[:, 0] / wsum.to(device=dev, dtype=torch.float64)
+    if not grad:
+        return f, None, None, None, None
+    o = 1
+    db1 = out[:, o:o + h1]
+    o += h1p
+    tail = []
+    if h2:
+        tail.append((out[:, o:o + h1p * h2p].view(P, h1p, h2p)[:, :h1, :h2], out[:, o + h1p * h2p:o + h1p * h2p + h2]))
+        o += h1p * h2p + h2p
+    inl, inlp = (h2, h2p) if h2 else (h1, h1p)
+    tail.append((out[:, o:o + inlp * 16].view(P, inlp, 16)[:, :inl, :K], out[:, o + inlp * 16:o + inlp * 16 + K]))
+    return f, tail, db1, dW1, dZ1
 
 
 def _n_blocks(N: int, grad: bool = True) -> int:
