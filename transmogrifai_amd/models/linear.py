@@ -186,7 +186,11 @@ class BatchedObjective:
 class MultinomialObjective:
     """Softmax cross-entropy of P problems with K classes; ``U`` is ``[(d+1)*K, P]`` laid out as
     ``[d+1, K]`` blocks (class-major coefficient columns), so the batched OWL-QN is reused unchanged.
-    One GEMM ``X [N,d] @ V [d, P*K]`` produces every problem's class margins."""
+    One GEMM ``X [N,d] @ V [d, P*K]`` produces every problem's class margins, followed on the GPU by one fused softmax
+    epilogue. On a :class:`~transmogrifai_amd.ops.linear.SparseDesign` with up to 16 classes (``self.sparse``) the
+    margins, the softmax and the sums are one launch from the CSR non-zeros instead (``ops/linear.py``
+    ``sparse_mnl_pass``; ``TMOG_MNL_SPARSE_FUSED=0`` keeps the product and the epilogue): no ``[N, P*K]`` margin array,
+    and a value pass writes nothing per row."""
 
     def __init__(self, X, y, W, inv_std, l2, fit_intercept, K, par=None, wcols=None):
         self.X, self.W, self.K = X, W, K
@@ -207,6 +211,16 @@ class MultinomialObjective:
             pos = {c: i for i, c in enumerate(uniq)}
             self.Wb = W.to(torch.float32)[:, uniq].contiguous()
             self.wmap = torch.tensor([pos[c] for c in wc], dtype=torch.int32).to(X.device)
+        # a sparse design: margins from the CSR non-zeros, softmax and sums in one launch (sparse_mnl_kernels.hip),
+        # reading one weight column per distinct training-row set
+        self.sparse = self.fused and LK.sparse_mnl_supported(X, K) and LK.sparse_mnl_enabled()
+        if self.sparse:
+            wc = list(range(P)) if wcols is None else list(wcols)
+            uniq = sorted(set(wc))
+            pos = {c: i for i, c in enumerate(uniq)}
+            self.Wb = W[:, uniq].to(torch.float32).contiguous()
+            self.wmap = LK.weight_map([pos[c] for c in wc], P, X.device)
+            self.yf = y.to(device=X.device, dtype=torch.float32).contiguous()
         self.y = y
         self.Y = None if self.fused else torch.nn.functional.one_hot(y.to(torch.int64), K).to(X.dtype)    # [N, K]
         self.wsum = _psum(par, W.sum(0).to(torch.float64))[0].clamp_min(1e-300)
@@ -251,13 +265,21 @@ class MultinomialObjective:
         f, rs = LK.softmax_objective(M, self.y, self.W, b.t().reshape(-1), P, self.K, grad)
         return B, M, f, rs
 
+    def _sparse_pass(self, U, grad):
+        B, V, b = self._split(U)
+        P = U.shape[1]
+        self.passes += 1
+        f, rs, R = LK.sparse_mnl_pass(self.X, self.yf, self.Wb, V.permute(0, 2, 1).reshape(self.d, P * self.K),
+                                      b.t().reshape(-1), P, self.K, grad, wmap=self.wmap)
+        return B, R, f, rs
+
     def value(self, U):
         if self.Xb is not None:
             B, f, _, _ = self._bf16_pass(U, False)
             f = _psum(self.par, f)[0] / self.wsum
             return f + 0.5 * self.l2 * (B[:self.d] ** 2).sum((0, 1))
         if self.fused:
-            B, _, f, _ = self._fused_pass(U, False)
+            B, _, f, _ = self._sparse_pass(U, False) if self.sparse else self._fused_pass(U, False)
             f = _psum(self.par, f)[0] / self.wsum
             return f + 0.5 * self.l2 * (B[:self.d] ** 2).sum((0, 1))
         M = self.margins(U)
@@ -273,7 +295,7 @@ class MultinomialObjective:
                 B, fs, rs, Gs = self._bf16_pass(U, True)
                 fs, Gs, rs = _psum(self.par, fs, Gs, rs)
             else:
-                B, R, fs, rs = self._fused_pass(U, True)
+                B, R, fs, rs = self._sparse_pass(U, True) if self.sparse else self._fused_pass(U, True)
                 fs, Gs, rs = _psum(self.par, fs, LK.gemm_t(self.X, R).to(torch.float64), rs)
             f = fs / self.wsum
             G = Gs.reshape(self.d, P, self.K).permute(0, 2, 1) / self.wsum[None, None, :]   # [d, K, P]

@@ -191,6 +191,21 @@ int tmog_hip_sparse_lr_objective(const int64_t* row_ptr, const int32_t* col, con
                                  int grad, float* R, int ldr, double* f_part, double* r_part, int nblk, double* f,
                                  double* r, hipStream_t stream);
 
+// ---- hip/sparse_mnl_kernels.hip: the fused multinomial objective on a sparse design, P problems of 2 <= K <= 16
+// classes, columns p*K + k (Vs [ds][ldv], Xd / Vd / madd / W / wmap as for tmog_hip_sparse_lr_objective, nd <=
+// tmog_hip_sparse_mnl_nd_max(); y holds class ids, one outside [0, K): loss 0, no one-hot term). A launch runs
+// chunk = tmog_hip_sparse_mnl_chunk(P, K) problems side by side on rows = tmog_hip_sparse_mnl_rows(P, K) rows a wave
+// (both 0 for an unsupported P or K); f_part / r_part hold nblk x ceil(P / chunk) x (64 / rows) doubles; out
+// [P + P*K] is f [P] then rsum [P*K], their sums in a fixed order; R [N][ldr] is written only with grad
+int tmog_hip_sparse_mnl_nd_max();
+int tmog_hip_sparse_mnl_chunk(int P, int K);
+int tmog_hip_sparse_mnl_rows(int P, int K);
+int tmog_hip_sparse_mnl_objective(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t N,
+                                  const float* Vs, int ldv, const float* Xd, int nd, const float* Vd,
+                                  const float* madd, int ldm, const float* y, const float* W, int ldw,
+                                  const int32_t* wmap, int P, int K, const float* bias, int grad, float* R, int ldr,
+                                  double* f_part, double* r_part, int nblk, double* out, hipStream_t stream);
+
 // ---- hip/sparse_mlp_kernels.hip: one objective pass of P multilayer perceptrons (one or two sigmoid hidden layers
 // of width h1, h2 <= 64, h2 = 0 for one; softmax over 2 <= K <= 16 classes) on a sparse design, nd <=
 // tmog_hip_sparse_mlp_nd_max(). Per problem: W1s [ds][h1], W1d [nd][h1], b1 [h1], Wm [h1][h2], bm [h2] (h2 > 0),

@@ -7,7 +7,8 @@ library-shaped GEMMs, fp32 in / fp32 accumulate), on the host through BLAS.
 What runs where on the device: a dense fp32 design up to 384 columns -- ``fused_objective``
 (``linear_kernels.hip``, one pass), up to 2048 -- library GEMM + ``lr_epilogue_grad``; its bf16 copy --
 ``fused_objective_bf16`` / ``mnl_objective_bf16``; a :class:`SparseDesign` -- products on ``sparse_kernels.hip``,
-the multinomial epilogue ``softmax_objective``, the binary objective ``sparse_fused_objective``
+the multinomial objective ``sparse_mnl_pass`` (``sparse_mnl_kernels.hip``: margins, softmax and sums in one launch;
+above 16 classes the epilogue ``softmax_objective`` over the product), the binary objective ``sparse_fused_objective``
 (``sparse_lr_kernels.hip``: margins, loss and sums in one launch, ``X^T R`` on ``csc_spmm_t_kernel``), the
 regression learners' fp64 weighted Grams ``SparseDesign.wgram`` and IRLS margins ``SparseDesign.mm64``
 (``sparse_gram_kernels.hip``: the Gram's sparse rows from the non-zeros, the dense block's on ``wgram_kernel``), and the
@@ -396,7 +397,73 @@ def sparse_fused_objective(D: "SparseDesign", y: torch.Tensor, W: torch.Tensor, 
     return f, r, (D.tmm(R) if grad else None)
 
 
-_MLP_DZ1_BYTES = 1 << 30      # sparse_mlp_pass: problems per launch keep dZ1 [N, Pg * h1] fp32 within 1 GiB
+def sparse_mnl_supported(D, K: int) -> bool:
+    """The fused multinomial pass (``sparse_mnl_pass``) serves a :class:`SparseDesign` on the GPU with at least one
+    row and 2 to 16 classes (a problem's classes share a group of 4, 8 or 16 lanes)."""
+    return isinstance(D, SparseDesign) and D.device.type == "cuda" and D.shape[0] > 0 and 2 <= int(K) <= 16
+
+
+def sparse_mnl_enabled() -> bool:
+    """``TMOG_MNL_SPARSE_FUSED=0`` restores the unfused multinomial pass on a sparse design (dense-block GEMM, CSR
+    product into ``M [N, P*K]``, ``softmax_objective`` over it). On by default: at 1M x 1352, 40 non-zeros a row,
+    24 problems of 6 classes the fused value pass measured 2.12 ms against 2.68 ms, value + gradient 7.09 against
+    8.39 ms and a multinomial ``OpLogisticRegression.fit_batch`` 282 against 326 ms (profiles/sparse_mnl.txt)."""
+    return os.environ.get("TMOG_MNL_SPARSE_FUSED", "1") != "0"
+
+
+def sparse_mnl_pass(D: "SparseDesign", y: torch.Tensor, W: torch.Tensor, V: torch.Tensor, bias: torch.Tensor, P: int,
+                    K: int, grad: bool = True, wmap: Optional[torch.Tensor] = None,
+                    R: Optional[torch.Tensor] = None):
+    """One launch of ``ops/csrc/hip/sparse_mnl_kernels.hip`` for ``P`` problems of ``K`` classes (``V [d, P*K]``,
+    ``bias [P*K]``, problem-major columns ``p*K + k``): the class margins ``m = X V + bias`` row by row from the CSR
+    non-zeros and the dense block, their softmax and the fp64 sums, without an ``[N, P*K]`` margin array. Returns
+    ``(f [P], rsum [P*K], R)`` with ``f = sum_i W (lse - m_y)`` and ``rsum = sum_i R`` in fp64 and, with ``grad``,
+    ``R [N, P*K] = W (softmax - onehot(y))`` in fp32 (written into the caller's ``R`` when given: fp32, unit column
+    stride); a value pass writes nothing per row. A label outside ``[0, K)`` gives loss 0 and no one-hot term.
+    Problem p's row weights are column ``wmap[p]`` of ``W`` (device int32; default column p). A dense block wider
+    than the kernel keeps in LDS (``tmog_hip_sparse_mnl_nd_max``) is multiplied by the library GEMM and enters the
+    kernel as an addend."""
+    from . import _native as N_
+    if not sparse_mnl_supported(D, K):
+        raise ValueError("sparse_mnl_pass: unsupported design or class count (sparse_mnl_supported)")
+    lib = N_.hip()
+    dev = D.device
+    N, P, K = int(D.shape[0]), int(P), int(K)
+    C = P * K
+    V = V.to(device=dev, dtype=torch.float32)
+    if V.shape != (D.shape[1], C):
+        raise ValueError("sparse_mnl_pass: V must be [d, P * K]")
+    Vs = V.index_select(0, D.idx_s).contiguous()
+    nd = int(D.idx_d.numel())
+    Vd = V.index_select(0, D.idx_d).contiguous()
+    Xd, madd = (D.Xd if nd else None), None
+    if nd > int(lib.tmog_hip_sparse_mnl_nd_max()):
+        Xd, madd = None, (D.Xd @ Vd).contiguous()
+    yf = y.to(device=dev, dtype=torch.float32).contiguous()
+    Wf = W.to(torch.float32).contiguous()
+    if wmap is None:
+        wmap = torch.arange(P, dtype=torch.int32, device=dev)
+    bf = bias.to(device=dev, dtype=torch.float32).contiguous()
+    chunk, rows = int(lib.tmog_hip_sparse_mnl_chunk(P, K)), int(lib.tmog_hip_sparse_mnl_rows(P, K))
+    nchunk = (P + chunk - 1) // chunk
+    # persistent workgroups of 4 waves, `rows` rows a wave at a time: up to 4 per CU, each with work
+    groups = (N + rows - 1) // rows
+    nblk = max(1, min((groups + 3) // 4, torch.cuda.get_device_properties(dev).multi_processor_count * 4))
+    part = torch.empty(2, nblk, nchunk * (64 // rows), dtype=torch.float64, device=dev)
+    out = torch.empty(P + C, dtype=torch.float64, device=dev)   # the partials, folded in a fixed order by the launch
+    if grad and R is None:
+        R = torch.empty(N, C, dtype=torch.float32, device=dev)
+    if R is not None and not (R.dtype == torch.float32 and R.shape == (N, C) and R.stride(1) == 1):
+        raise ValueError("sparse_mnl_pass: R must be fp32 [N, P * K] with unit column stride")
+    N_.check(lib.tmog_hip_sparse_mnl_objective(
+        N_.ptr(D.row_ptr), N_.ptr(D.col), N_.ptr(D.val), N, N_.ptr(Vs), C, N_.ptr(Xd), nd, N_.ptr(Vd),
+        N_.ptr(madd), C, N_.ptr(yf), N_.ptr(Wf), Wf.shape[1], N_.ptr(wmap), P, K, N_.ptr(bf), int(grad), N_.ptr(R),
+        0 if R is None else R.stride(0), N_.ptr(part[0]), N_.ptr(part[1]), nblk, N_.ptr(out), N_.stream(dev)),
+        "sparse_mnl_objective")
+    return out[:P], out[P:], (R if grad else None)
+
+
+_MLP_DZ1_BYTES = 1 << 30     # sparse_mlp_pass: problems per launch keep dZ1 [N, Pg * h1] fp32 within 1 GiB
 
 
 def sparse_mlp_supported(D, layers) -> bool:
