@@ -71,7 +71,7 @@ def parse_abi(text: str):
 
 
 _HOST_ABI, _STRUCT_FIELDS, ABI_CONSTS = parse_abi((build.CSRC / "common" / "tmog_abi.h").read_text())
-_HIP_ABI = parse_abi((build.CSRC / "hip" / "tmog_hip_abi.h").read_text())[0]
+_HIP_ABI, _, HIP_CONSTS = parse_abi((build.CSRC / "hip" / "tmog_hip_abi.h").read_text())
 _HOST_SIGS = {name: args for name, (_, args) in _HOST_ABI.items()}
 _HIP_SIGS = {name: args for name, (_, args) in _HIP_ABI.items()}
 _RESTYPES = {name: res for name, (res, _) in {**_HOST_ABI, **_HIP_ABI}.items()}

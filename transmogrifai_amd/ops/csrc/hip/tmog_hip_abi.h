@@ -177,6 +177,25 @@ int tmog_hip_softmax_epilogue(float* M, int64_t N, int P, int K, const float* bi
                               int ldw, float* Lw, int grad, hipStream_t stream);
 int tmog_hip_colsum(const float* R, int64_t N, int C, int nblk, double* part, hipStream_t stream);
 
+// ---- hip/sparse_build_kernels.hip: the CSR and the CSC of the non-zeros of a dense device matrix X [N][d] (fp32, or
+// fp64 with f64; row stride ldx elements, unit column stride; d <= TMOG_SPARSE_BUILD_DMAX, N < 2^31), in row tiles of
+// TMOG_SPARSE_BUILD_TR rows, T = ceil(N / TR) of them. tmog_hip_sparse_build_count writes tile_cnt [T][d] (non-zeros
+// of a column in a tile) and nz [d] (of a column). tmog_hip_sparse_build_fill takes smap [d] (a column's rank among the
+// kept columns, ascending, or -1) and col_start [kept + 1] (the kept columns' first CSC positions, the scan of their
+// nz) and writes row_ptr [N + 1], col / val [nnz] (CSR, row-major, columns ascending) and csc_row [nnz] (CSC,
+// column-major, rows ascending), csc_val / csc_val_sq / csc_pos [nnz] (the value, its square, the CSR position; each
+// skipped when null) and row_sum [N] (fp64, a row's values added in column order; skipped when null). Scratch:
+// tile_off [T][d] int32, tile_nnz [T], tile_start [T + 1]. No atomics: two runs write the same bits
+#define TMOG_SPARSE_BUILD_TR 64
+#define TMOG_SPARSE_BUILD_DMAX 16384
+int tmog_hip_sparse_build_count(const void* X, int f64, int64_t ldx, int64_t N, int d, uint8_t* tile_cnt, int64_t* nz,
+                                hipStream_t stream);
+int tmog_hip_sparse_build_fill(const void* X, int f64, int64_t ldx, int64_t N, int d, const int32_t* smap,
+                               const int64_t* col_start, const uint8_t* tile_cnt, int32_t* tile_off,
+                               int32_t* tile_nnz, int64_t* tile_start, int64_t* row_ptr, int32_t* col, float* val,
+                               int32_t* csc_row, float* csc_val, float* csc_val_sq, int64_t* csc_pos,
+                               double* row_sum, hipStream_t stream);
+
 // ---- hip/sparse_lr_kernels.hip: the fused binary objective on a sparse design (CSR of the sparse columns with
 // Vs [ds][ldv], dense block Xd [N][nd] with Vd [nd][ldv], nd <= tmog_hip_sparse_lr_nd_max(); Xd null: no dense block
 // in the kernel, madd [N][ldm] -- or null -- is added to the margins instead). Problem p weighs row i by

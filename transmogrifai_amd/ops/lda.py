@@ -19,14 +19,23 @@ class DocTermCSR:
     """The non-zeros of a dense term-count matrix ``X [N, V]``: CSR (``row_ptr`` int64, ``col`` int32 sorted per
     row, ``val`` fp32), their segmented CSC (``csc_row`` int32, ``seg_begin`` / ``col_seg`` int64, segments of at
     most 4096 non-zeros of one column), ``csc_pos`` (the CSR position of every CSC entry) and ``row_sum`` (fp64).
-    Built in row chunks with torch ops only, on the device of ``X``. Values are kept as fp32: term counts are exact,
-    an fp64 column of other values (tf-idf weights, counts above 2**24) is rounded where the dense path is not."""
+    Built on the device of ``X``: by ``ops.linear.csr_csc_build`` (``ops/csrc/hip/sparse_build_kernels.hip``; an fp32 or
+    fp64 device matrix of at most 16384 columns, ``row_sum`` added in column order), otherwise, or with
+    ``TMOG_SPARSE_BUILD=0``, in row chunks with torch ops. Values are kept as fp32: term counts are exact, an fp64
+    column of other values (tf-idf weights, counts above 2**24) is rounded where the dense path is not."""
 
     def __init__(self, X: torch.Tensor, chunk: int = 1 << 16):
+        from .linear import csr_csc_build, sparse_build_enabled, sparse_build_supported
         dev = X.device
         N, V = X.shape
         self.shape = (N, V)
         self.device = dev
+        if sparse_build_enabled() and sparse_build_supported(X):
+            B = csr_csc_build(X, None, _SEG_NNZ, want_pos=True, want_row_sum=True, want_val=False)
+            for name in ("nnz", "row_ptr", "col", "val", "row_sum", "csc_pos", "csc_row", "col_seg", "n_seg",
+                         "seg_begin"):
+                setattr(self, name, B[name])
+            return
         rows, cols, vals = [], [], []
         for a in range(0, N, chunk):
             Xc = X[a:a + chunk]

@@ -12,7 +12,8 @@ above 16 classes the epilogue ``softmax_objective`` over the product), the binar
 (``sparse_lr_kernels.hip``: margins, loss and sums in one launch, ``X^T R`` on ``csc_spmm_t_kernel``), the
 regression learners' fp64 weighted Grams ``SparseDesign.wgram`` and IRLS margins ``SparseDesign.mm64``
 (``sparse_gram_kernels.hip``: the Gram's sparse rows from the non-zeros, the dense block's on ``wgram_kernel``), and the
-MLP classifier's whole objective pass ``sparse_mlp_pass`` (``sparse_mlp_kernels.hip``).
+MLP classifier's whole objective pass ``sparse_mlp_pass`` (``sparse_mlp_kernels.hip``). The design itself is built by
+``csr_csc_build`` (``sparse_build_kernels.hip``: counts, scans and one fill pass, no sort).
 """
 from __future__ import annotations
 
@@ -69,6 +70,9 @@ class SparseDesign:
         N, d = X.shape
         self.shape = (N, d)
         self.device, self.dtype = dev, torch.float32
+        if sparse_build_enabled() and sparse_build_supported(X):
+            self._build_on_device(X)
+            return
         nz = torch.zeros(d, dtype=torch.int64, device=dev)
         for a in range(0, N, chunk):
             nz += (X[a:a + chunk] != 0).sum(0)
@@ -109,6 +113,25 @@ class SparseDesign:
         self.seg_begin = torch.cat([col_start[seg_col] + within * _SEG_NNZ,
                                     torch.tensor([self.nnz], dtype=torch.int64, device=dev)]).contiguous()
         self.n_seg = n_seg
+
+    def _build_on_device(self, X: torch.Tensor):
+        """The same fields from ``ops/csrc/hip/sparse_build_kernels.hip`` (``csr_csc_build``): the column counts come
+        from the first kernel, the dense / sparse rule is applied to them here."""
+        N, d = X.shape
+        tile_cnt, nz = sparse_column_counts(X)
+        dense = nz > self.DENSE_FRAC * max(N, 1)
+        host = torch.stack([nz, dense.to(torch.int64)]).cpu()      # the build's one synchronisation
+        dense_h = host[1] != 0
+        idx_d, idx_s = torch.nonzero(dense_h).reshape(-1), torch.nonzero(~dense_h).reshape(-1)
+        self.idx_d, self.idx_s = idx_d.to(X.device), idx_s.to(X.device)
+        self.Xd = X.index_select(1, self.idx_d).to(torch.float32).contiguous()
+        self.ds = int(idx_s.numel())
+        smap = torch.full((d,), -1, dtype=torch.int32)
+        smap[idx_s] = torch.arange(self.ds, dtype=torch.int32)
+        B = csr_csc_build(X, smap, _SEG_NNZ, counts=(tile_cnt, host[0]))
+        for name in ("nnz", "row_ptr", "col", "val", "csc_row", "csc_val", "csc_val_sq", "col_seg", "seg_begin",
+                     "n_seg"):
+            setattr(self, name, B[name])
 
     @staticmethod
     def worthwhile(X: torch.Tensor) -> bool:
@@ -286,6 +309,106 @@ def sparse_gram_design(X) -> Optional["SparseDesign"]:
         return None
     D = SparseDesign(X)
     return D if sparse_wgram_supported(D) else None
+
+
+def sparse_build_enabled() -> bool:
+    """``TMOG_SPARSE_BUILD=0`` restores the torch build of :class:`SparseDesign` and ``ops.lda.DocTermCSR`` (row
+    chunks of ``nonzero``, a 64-bit ``argsort`` of the pairs). On by default: at 1M x 1352, 40 non-zeros a row,
+    ``SparseDesign(X)`` measured 6.5 ms against 29.0 ms and 0.95 GB of peak memory against 4.2 GB, ``DocTermCSR(X)``
+    6.9 against 81.8 ms, a binary ``OpLogisticRegression.fit_batch`` 62 against 84 ms; at 4096 x 256 the build 0.27
+    against 0.65 ms (profiles/sparse_build.txt)."""
+    return os.environ.get("TMOG_SPARSE_BUILD", "1") != "0"
+
+
+def sparse_build_supported(X) -> bool:
+    """``csr_csc_build`` serves an fp32 or fp64 device matrix with unit column stride and any row stride, at least one
+    row and fewer than 2**31, and 1 to ``TMOG_SPARSE_BUILD_DMAX`` = 16384 columns (``fill_kernel`` keeps 64 rows x
+    d / 64 column groups of 16-bit counts in LDS). Anything else keeps the torch build."""
+    from . import _native as N_
+    return isinstance(X, torch.Tensor) and X.is_cuda and X.dim() == 2 and X.layout == torch.strided \
+        and X.dtype in (torch.float32, torch.float64) and 1 <= X.shape[0] < 2 ** 31 \
+        and 1 <= X.shape[1] <= N_.HIP_CONSTS["TMOG_SPARSE_BUILD_DMAX"] and X.stride(0) >= 0 \
+        and (X.stride(1) == 1 or X.shape[1] == 1)
+
+
+def sparse_column_counts(X: torch.Tensor):
+    """``count_kernel`` and its fold (``ops/csrc/hip/sparse_build_kernels.hip``), one read of ``X``: ``(tile_cnt, nz)``
+    with ``nz [d]`` int64 the non-zeros of every column and ``tile_cnt [T, d]`` uint8 those of every column in every
+    tile of ``TMOG_SPARSE_BUILD_TR`` rows, which ``csr_csc_build`` takes as ``counts``. Nothing is copied to the host."""
+    from . import _native as N_
+    if not sparse_build_supported(X):
+        raise ValueError("sparse_column_counts: unsupported matrix (sparse_build_supported)")
+    N, d = X.shape
+    T = -(-N // N_.HIP_CONSTS["TMOG_SPARSE_BUILD_TR"])
+    tile_cnt = torch.empty(T, d, dtype=torch.uint8, device=X.device)
+    nz = torch.empty(d, dtype=torch.int64, device=X.device)
+    N_.check(N_.hip().tmog_hip_sparse_build_count(N_.ptr(X), int(X.dtype == torch.float64), X.stride(0), N, d,
+                                                  N_.ptr(tile_cnt), N_.ptr(nz), N_.stream(X.device)),
+             "sparse_build_count")
+    return tile_cnt, nz
+
+
+def csr_csc_build(X: torch.Tensor, smap: Optional[torch.Tensor], seg: int, want_pos: bool = False,
+                  want_row_sum: bool = False, want_val: bool = True, counts=None) -> dict:
+    """The CSR and the segmented CSC of the kept columns of a dense device matrix, on
+    ``ops/csrc/hip/sparse_build_kernels.hip`` (no sort, no atomics: two builds are bitwise equal). ``smap [d]`` int32
+    gives a column's rank among the kept columns, ascending, or -1 (None: every column is kept); ``seg`` is the
+    segment length of the CSC. An entry is a value with ``x != 0`` in the source dtype, stored as its fp32 rounding.
+
+    Returns the fields of :class:`SparseDesign` by name: ``nnz``, ``n_seg``, ``row_ptr [N + 1]`` int64, ``col`` int32,
+    ``val`` fp32 (row-major, columns ascending), ``csc_row`` int32 (column-major, rows ascending), ``col_seg [ds + 1]``
+    and ``seg_begin [n_seg + 1]`` int64; with ``want_val`` ``csc_val`` and ``csc_val_sq``, with ``want_pos``
+    ``csc_pos`` (int64, the CSR position of a CSC entry), with ``want_row_sum`` ``row_sum [N]`` (fp64, a row's values
+    added in column order). ``counts`` is ``(tile_cnt, nz on the host)`` when the caller already ran
+    ``sparse_column_counts``. The column counts are scanned on the host (``d`` numbers): one synchronisation."""
+    from . import _native as N_
+    if not sparse_build_supported(X):
+        raise ValueError("csr_csc_build: unsupported matrix (sparse_build_supported)")
+    dev = X.device
+    N, d = X.shape
+    seg = int(seg)
+    if counts is None:
+        tile_cnt, nz = sparse_column_counts(X)
+        nz = nz.cpu()
+    else:
+        tile_cnt, nz = counts
+    smap = torch.arange(d, dtype=torch.int32) if smap is None else smap.to(device="cpu", dtype=torch.int32)
+    cnt = nz[smap >= 0]
+    ds = int(cnt.numel())
+    col_start = torch.zeros(ds + 1, dtype=torch.int64)
+    col_start[1:] = torch.cumsum(cnt, 0)
+    nnz = int(col_start[-1])
+    nseg = (cnt + seg - 1) // seg
+    col_seg = torch.zeros(ds + 1, dtype=torch.int64)
+    col_seg[1:] = torch.cumsum(nseg, 0)
+    n_seg = int(col_seg[-1])
+    seg_col = torch.repeat_interleave(torch.arange(ds), nseg)
+    within = torch.arange(n_seg) - col_seg[seg_col]
+    seg_begin = torch.cat([col_start[seg_col] + within * seg, torch.tensor([nnz], dtype=torch.int64)])
+    T = tile_cnt.shape[0]
+    out = {"nnz": nnz, "n_seg": n_seg, "col_seg": col_seg.to(dev), "seg_begin": seg_begin.to(dev).contiguous(),
+           "row_ptr": torch.empty(N + 1, dtype=torch.int64, device=dev),
+           "col": torch.empty(nnz, dtype=torch.int32, device=dev),
+           "val": torch.empty(nnz, dtype=torch.float32, device=dev),
+           "csc_row": torch.empty(nnz, dtype=torch.int32, device=dev)}
+    if want_val:
+        out["csc_val"] = torch.empty(nnz, dtype=torch.float32, device=dev)
+        out["csc_val_sq"] = torch.empty(nnz, dtype=torch.float32, device=dev)
+    if want_pos:
+        out["csc_pos"] = torch.empty(nnz, dtype=torch.int64, device=dev)
+    if want_row_sum:
+        out["row_sum"] = torch.empty(N, dtype=torch.float64, device=dev)
+    smap_d, col_start_d = smap.to(dev), col_start.to(dev)
+    tile_off = torch.empty(T, d, dtype=torch.int32, device=dev)
+    tile_nnz = torch.empty(T, dtype=torch.int32, device=dev)
+    tile_start = torch.empty(T + 1, dtype=torch.int64, device=dev)
+    N_.check(N_.hip().tmog_hip_sparse_build_fill(
+        N_.ptr(X), int(X.dtype == torch.float64), X.stride(0), N, d, N_.ptr(smap_d), N_.ptr(col_start_d),
+        N_.ptr(tile_cnt), N_.ptr(tile_off), N_.ptr(tile_nnz), N_.ptr(tile_start), N_.ptr(out["row_ptr"]),
+        N_.ptr(out["col"]), N_.ptr(out["val"]), N_.ptr(out["csc_row"]), N_.ptr(out.get("csc_val")),
+        N_.ptr(out.get("csc_val_sq")), N_.ptr(out.get("csc_pos")), N_.ptr(out.get("row_sum")), N_.stream(dev)),
+        "sparse_build_fill")
+    return out
 
 
 def softmax_objective(M: torch.Tensor, y: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, P: int, K: int,
