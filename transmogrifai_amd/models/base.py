@@ -151,6 +151,25 @@ class Learner:
         raise NotImplementedError(f"{self.name} has no path-perturbation LOCO; RecordInsightsLOCO's rescore mode "
                                   "explains any model")
 
+    def linear_margins(self, state):
+        """The fitted state as a margin model ``score = link(b + W^T x)`` (linear-margin learners):
+        ``(W float64 [d, C_m], b float64 [C_m], link, link parameter)`` with a link name of ``ops.loco.LINKS``.
+        Zeroing a column moves the margin by its ``-W[j, :] x_j``, which makes ``RecordInsightsLOCO``'s margins mode
+        exact without rescoring. ``ValueError`` for a state whose link has no device code or that has more than
+        ``ops.loco.MAX_MARGINS`` margin columns."""
+        raise NotImplementedError(f"{self.name} is no linear-margin model; RecordInsightsLOCO's rescore mode "
+                                  "explains any model")
+
+    @staticmethod
+    def _margin_model(W, b, link: str, param: float = 0.0):
+        from ..ops.loco import MAX_MARGINS
+        W = torch.as_tensor(np.asarray(W, np.float64)).reshape(len(W), -1)
+        b = torch.as_tensor(np.asarray(b, np.float64)).reshape(-1)
+        if W.shape[1] > MAX_MARGINS:
+            raise ValueError(f"perturbation='margins' serves at most {MAX_MARGINS} margin columns, the model has "
+                             f"{W.shape[1]} (use 'rescore')")
+        return W, b, link, float(param)
+
     def partial_dependence(self, state, X: torch.Tensor, columns, rows=None, context=None, scale: str = "raw",
                            ice: bool = False):
         """Exact partial dependence of the model's score on each of ``columns`` over the model's own bin grid (tree

@@ -173,6 +173,20 @@ class GeneralizedLinearRegressionLearner(Learner):
         e = torch.zeros(mu.shape[0], 0, dtype=torch.float64, device=X.device)
         return mu, e, e
 
+    # inverse link of `_link` -> link of the margins kernel (ops/loco.py LINKS)
+    _MARGIN_LINKS = {"identity": "identity", "log": "exp", "inverse": "inverse", "logit": "sigmoid", "sqrt": "square"}
+
+    def linear_margins(self, state):
+        link, lp = state["link"], float(state.get("link_power", 0.0) or 0.0)
+        if link == "power":
+            kind = "exp" if lp == 0 else "power"
+        elif link in self._MARGIN_LINKS:
+            kind = self._MARGIN_LINKS[link]
+        else:
+            raise ValueError(f"perturbation='margins' has no device code for the {link} link of {self.name} "
+                             "(use 'rescore')")
+        return self._margin_model(state["coefficients"], [state["intercept"]], kind, lp)
+
     def feature_contributions(self, state, d):
         return np.asarray(state["coefficients"], np.float64)
 

@@ -730,6 +730,12 @@ class LogisticRegressionLearner(_LinearBase):
             return self._multinomial_outputs(state, X)
         return probability_outputs(self.margin(state, X), threshold=state.get("threshold", 0.5))
 
+    def linear_margins(self, state):
+        if "coefficient_matrix" in state:
+            return self._margin_model(np.asarray(state["coefficient_matrix"], np.float64).T, state["intercepts"],
+                                      "softmax")
+        return self._margin_model(state["coefficients"], [state["intercept"]], "binary")
+
     def predict_batch(self, states, X, rows, context=None):
         if not states:
             return []
@@ -771,6 +777,9 @@ class LinearSVCLearner(LogisticRegressionLearner):
         raw = torch.stack([-m, m], 1)
         pred = (m > state.get("threshold", 0.0)).to(torch.float64)
         return pred, raw, torch.zeros(m.shape[0], 0, dtype=torch.float64, device=m.device)
+
+    def linear_margins(self, state):
+        return self._margin_model(state["coefficients"], [state["intercept"]], "step", state.get("threshold", 0.0))
 
     def predict_batch(self, states, X, rows, context=None):
         return Learner.predict_batch(self, states, X, rows, context)
@@ -911,6 +920,9 @@ class LinearRegressionLearner(_LinearBase):
         e = torch.zeros(m.shape[0], 0, dtype=torch.float64, device=m.device)
         return m, e, e
 
+    def linear_margins(self, state):
+        return self._margin_model(state["coefficients"], [state["intercept"]], "identity")
+
     def feature_contributions(self, state, d):
         return np.asarray(state["coefficients"], np.float64)
 
@@ -962,6 +974,14 @@ class NaiveBayesLearner(Learner):
             raw = Xd @ th.t() + pi[None, :]
         prob = torch.softmax(raw, 1)
         return torch.argmax(prob, 1).to(torch.float64), raw, prob
+
+    def linear_margins(self, state):
+        pi = torch.as_tensor(np.asarray(state["pi"], np.float64))
+        th = torch.as_tensor(np.asarray(state["theta"], np.float64))           # [K, d]
+        if state.get("model_type") == "bernoulli":
+            neg = torch.log1p(-torch.exp(th).clamp(max=1 - 1e-12))
+            th, pi = th - neg, pi + neg.sum(1)
+        return self._margin_model(th.t().numpy(), pi.numpy(), "softmax")
 
     def feature_contributions(self, state, d):
         th = np.asarray(state["theta"])

@@ -114,6 +114,12 @@ int tmog_hip_forest_loco(const uint8_t* Xb, int F, int64_t n, const int32_t* row
                          const int32_t* tree_out, int missing_bin, int C, double scale, double* out,
                          hipStream_t stream);
 
+// ---- hip/loco_linear_kernels.hip
+int tmog_hip_loco_linear(const void* X, int x_fp64, int64_t n, int d, int64_t ldx, const double* W, const double* b,
+                         int Cm, int link, double link_param, const int32_t* cand_of_col, int n_plain, int G,
+                         const double* gsize, int top_k, int abs_mode, int leave_out, int64_t* cols, double* diffs,
+                         hipStream_t stream);
+
 // ---- hip/metric_kernels.hip
 int tmog_hip_binary_areas(const void* s, int is_f64, const int64_t* idx, int64_t n, int J, const uint8_t* lab,
                           double* out_pr, double* out_roc, hipStream_t stream);

@@ -14,6 +14,8 @@ elementwise [rows, d] tensor op); top-K selection per record is ``torch.topk`` o
 For tree models ``perturbation="paths"`` replaces the perturbed batches by exact path perturbation
 (``tree_engine.forest_loco``, HIP kernel ``ops/csrc/hip/loco_kernels.hip``): a zeroed column can change a tree's
 answer only where it is tested on the record's own path, so only those path suffixes are walked again.
+For linear-margin models ``perturbation="margins"`` does the same from the margin terms of the record's non-zeros
+(``ops.loco.loco_linear``, HIP kernel ``ops/csrc/hip/loco_linear_kernels.hip``, which also selects the top-K).
 
 Beyond the reference: ``RecordInsightsSHAP`` explains tree models with exact path-dependent TreeSHAP
 (``tree_engine.forest_shap``, HIP kernel ``ops/csrc/hip/shap_kernels.hip``) instead of perturbing columns, and
@@ -174,7 +176,7 @@ class RecordInsightsLOCO(UnaryTransformer):
     output_type = T.TextMap
     _defaults = {"top_k": 20, "top_k_strategy": "abs", "vector_aggregation_strategy": "Avg",
                  "perturbation": "rescore"}
-    PERTURBATIONS = ("rescore", "paths", "auto")
+    PERTURBATIONS = ("rescore", "paths", "auto", "margins")
 
     def __init__(self, model=None, uid=None, **kw):
         super().__init__(None, uid=uid, **kw)
@@ -201,11 +203,11 @@ class RecordInsightsLOCO(UnaryTransformer):
         """``perturbation``: ``rescore`` (default) scores one perturbed copy of the record per non-zero column;
         ``paths`` asks the learner for exact LOCO scores by tree-path perturbation (``Learner.loco_scores``, tree
         learners: ``tree_engine.forest_loco``) and is an error for a learner without them; ``auto`` takes paths
-        where the learner has them and rescores otherwise."""
+        where the learner has them and rescores otherwise; ``margins`` (:meth:`_margin_model`) is no path mode."""
         mode = self.params.get("perturbation", "rescore")
         if mode not in self.PERTURBATIONS:
             raise ValueError(f"perturbation must be one of {self.PERTURBATIONS}, got {mode!r}")
-        if mode == "rescore":
+        if mode in ("rescore", "margins"):
             return False
         from ...models.base import Learner
         learner = self._learner_state()[0]
@@ -214,6 +216,64 @@ class RecordInsightsLOCO(UnaryTransformer):
             raise ValueError(f"perturbation='paths' needs a tree learner with loco_scores, "
                              f"{getattr(learner, 'name', type(learner).__name__)} has none (use 'rescore' or 'auto')")
         return has
+
+    def _margin_model(self):
+        """``perturbation="margins"``: the learner's fitted state as ``link(b + W^T x)`` (``Learner.linear_margins``:
+        logistic regression, linear SVC, linear regression, GLM, naive Bayes), else None. Zeroing column ``j`` moves
+        the margin by exactly ``-W[j, :] x_j`` and a column group by the sum of those terms, so every score change
+        ``s(m) - s(m - t)`` follows in fp64 from one pass over the record's non-zeros: no perturbed batch is scored.
+        A device vector runs the HIP kernel behind ``ops.loco.loco_linear``, which also selects the top-K (ties keep
+        the earlier candidate); host vectors, ``transform_row`` and shapes beyond the kernel's limits fill the
+        candidate array from the same differences in torch and share the selection of the other modes. ``auto``
+        never selects this mode. A record with a NaN or infinite cell keeps whatever the arithmetic gives; nothing
+        is read or written out of bounds. An error for any other learner."""
+        if self.params.get("perturbation", "rescore") != "margins":
+            return None
+        from ...models.base import Learner
+        learner, state = self._learner_state()
+        if getattr(type(learner), "linear_margins", Learner.linear_margins) is Learner.linear_margins:
+            raise ValueError(f"perturbation='margins' needs a linear-margin learner, "
+                             f"{getattr(learner, 'name', type(learner).__name__)} is none (use 'rescore')")
+        return learner.linear_margins(state)
+
+    @staticmethod
+    def _link_scores(M: torch.Tensor, link: str, param: float) -> torch.Tensor:
+        """Scores ``[..., C]`` of fp64 margins ``[..., C_m]`` (the links of ``ops.loco.LINKS``)."""
+        if link == "softmax":
+            return torch.softmax(M, -1)
+        e = M[..., 0]
+        if link == "binary":
+            p1 = torch.sigmoid(e)
+            return torch.stack([1 - p1, p1], -1)
+        r = {"identity": lambda: e, "exp": lambda: torch.exp(e), "inverse": lambda: 1.0 / e,
+             "sigmoid": lambda: torch.sigmoid(e), "square": lambda: e * e,
+             "power": lambda: e.clamp_min(1e-12) ** (1.0 / param),
+             "step": lambda: (e > param).to(torch.float64)}[link]()
+        return r[..., None]
+
+    def _margins_block(self, X, model, plan):
+        """The margins mode of one block on the host formula: (base scores [n, C], explained score column [n],
+        candidate changes V [n, m, C] with group sums not yet divided, group changes under LeaveOutVector
+        [n, G, C])."""
+        W, b, link, param = model
+        cand_of_col, gsize, plain_col, gcols = plan
+        n, d = X.shape
+        dev = X.device
+        W, b = W.to(dev), b.to(dev)
+        if W.shape[0] != d:
+            raise ValueError(f"the model has {W.shape[0]} coefficients, the vector {d} columns")
+        Tm = X.to(torch.float64)[:, :, None] * W[None]                       # [n, d, C_m]
+        M = b[None, :] + Tm.sum(1)
+        base = self._link_scores(M, link, param)
+        C = base.shape[1]
+        ex = torch.full((n,), 1 if C == 2 else 0, dtype=torch.long, device=dev) if C <= 2 else M.argmax(1)
+        diff = base[:, None, :] - self._link_scores(M[:, None, :] - Tm, link, param)
+        diff = torch.where((X != 0)[:, :, None], diff, torch.zeros_like(diff))
+        V = torch.zeros(n, int(gsize.numel()), C, dtype=torch.float64, device=dev)
+        V.index_add_(1, cand_of_col, diff)
+        V = V / gsize[None, :, None]
+        out = [base - self._link_scores(M - Tm[:, g].sum(1), link, param) for g in gcols]
+        return base, ex, V, out
 
     def _paths_diffs(self, X: torch.Tensor, gcols):
         """Score changes from the learner's path-perturbation LOCO: (per used column [n, U, C], per column group
@@ -296,20 +356,34 @@ class RecordInsightsLOCO(UnaryTransformer):
         n, d = X.shape
         dev = X.device
         paths = self._use_paths()
-        base, pred_cls = self._scores(X)
+        margins = self._margin_model()
+        plan = plan if plan is not None else self._plan(hist, d, dev)
+        cand_of_col, gsize, plain_col, gcols = plan
+        m = int(gsize.numel())
+        k = int(self.params["top_k"])
+        abs_mode = self.params["top_k_strategy"] == "abs"
+        leave_out = self.params["vector_aggregation_strategy"] != "Avg"
+        if margins is not None and X.is_cuda and m > 0 and n > 0:
+            from ...ops.loco import loco_linear
+            got = loco_linear(X, margins[0], margins[1], margins[2], margins[3], cand_of_col, m - len(gcols),
+                              gsize[m - len(gcols):], k, abs_mode, leave_out)
+            if got is not None:
+                return got
+        if margins is not None:
+            base, ex, MV, group_out = self._margins_block(X, margins, plan)
+        else:
+            base, pred_cls = self._scores(X)
         C = base.shape[1]
         if C == 0:
             raise RuntimeError("model does not produce scores for insights")
-        if C == 1:
+        if margins is not None:          # the explained column comes with the margins
+            pass
+        elif C == 1:
             ex = torch.zeros(n, dtype=torch.long, device=dev)
         elif C == 2:
             ex = torch.ones(n, dtype=torch.long, device=dev)
         else:
             ex = pred_cls.to(torch.long)
-        cand_of_col, gsize, plain_col, gcols = plan if plan is not None else self._plan(hist, d, dev)
-        m = int(gsize.numel())
-        k = int(self.params["top_k"])
-        abs_mode = self.params["top_k_strategy"] == "abs"
         kk = min(k, m)
         K = min(k if abs_mode else 2 * k, 2 * kk)
         if m == 0 or n == 0:
@@ -321,11 +395,12 @@ class RecordInsightsLOCO(UnaryTransformer):
             cu = cand_of_col[used]
             V = torch.zeros(n, m, C, dtype=torch.float64, device=dev)
             V.index_add_(1, cu, col_diff / gsize[cu][None, :, None])
+        elif margins is not None:
+            V = MV
         else:
             V = self._rescore_changes(X, nz, base, cand_of_col, gsize).view(n, m, C)
         Cc = plain_col[None, :].expand(n, m).clone()
         n_plain = m - len(gcols)
-        leave_out = self.params["vector_aggregation_strategy"] != "Avg"
         for g, gct in enumerate(gcols):
             active = nz[:, gct]
             has = active.any(1)
@@ -333,6 +408,8 @@ class RecordInsightsLOCO(UnaryTransformer):
                                                                                                     dtype=torch.long))
             if leave_out and paths:
                 V[:, n_plain + g] = torch.where(has[:, None], group_diff[:, g], torch.zeros_like(base))
+            elif leave_out and margins is not None:
+                V[:, n_plain + g] = torch.where(has[:, None], group_out[g], torch.zeros_like(base))
             elif leave_out:     # LeaveOutVector: zero every active column of the group at once
                 Xp = X.clone()
                 Xp[:, gct] = 0
@@ -352,6 +429,8 @@ class RecordInsightsLOCO(UnaryTransformer):
         okK = ok.gather(1, order)
         colsK = torch.where(okK, Cc.gather(1, sel), torch.full_like(sel, -1))
         diffsK = V.gather(1, sel[:, :, None].expand(n, K, C))
+        if margins is not None:          # as the kernel writes them: zeros where there is no insight
+            diffsK = torch.where(okK[:, :, None], diffsK, torch.zeros_like(diffsK))
         return colsK, diffsK
 
     def _run(self, X: torch.Tensor, hist: List[dict]):
