@@ -355,6 +355,9 @@ __global__ void __launch_bounds__(256) bf16_pack_kernel(const float* __restrict_
                                                         const int32_t* __restrict__ mode, const float* __restrict__ mu,
                                                         const float* __restrict__ sc, __bf16* __restrict__ B,
                                                         int64_t ldb, int64_t rows_per_blk) {
+  // the parts split the fp32-rounded c = (x - mu) * sc: contracted, c - h became fma(x - mu, sc, -h) on the unrounded
+  // product, and for a scale that is no power of two mid and lo were parts of another number than h
+#pragma clang fp contract(off)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t g = (int64_t)blockIdx.y * 64 + lane;
   if (g >= ldb / 8) return;                       // whole lanes idle: no barrier below
